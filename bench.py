@@ -1,17 +1,27 @@
 #!/usr/bin/env python3
 """Headline benchmark: differentiable ICP iterations (fwd+bwd) on B=256 x 16384-point clouds.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 Workload = BASELINE.json configs[2] ("C3"): per GPU B=256 synthetic scan pairs, n=m=16384,
 point-to-plane + Huber(1.0) + soft trim(5.0), differentiable, dim=3, float32, T_init=I.
 One "step" = one ICP iteration over the whole batch, forward AND backward: a timed call is
 ONE differentiable icp() call of K constant iterations, backward of T.sum() w.r.t. source and
 target, and (N>1) the RCCL all-gather of the poses, between barrier + device syncs.  Inputs are
-resident in HBM when timing starts.  `value` is the MEDIAN of --reps (>= 5) such calls made
-back to back after a steady-state warm-up ("warm-up 2 calls, then median of >= 5").
+resident in HBM when timing starts.  The timed steps are --reps such calls (default 1: exactly K
+timed steps), made after a W-iteration warm-up call and untimed K-iteration calls that bring the
+allocator and the chip to their steady state; `value` is the median over the timed calls and
+`ms_per_step` that call's time / K.
 
-Beside `value` the same run reports, each as the median of its own timed calls:
+--dump-outputs DIR writes what the last timed call returned -- T, pc, deltas, weights, costs, the stats and
+the gradients w.r.t. source and target -- as DIR/<name>.npy (float32 / float64).  An array of more than
+DUMP_ROWS rows (its last dimension when that is at most 16 wide, single elements otherwise) is written as
+a fixed sample of DUMP_ROWS of its rows (seed DUMP_SEED, the same rows for arrays of the same row count),
+a few MB in all.  The inputs depend on the arguments only, so two builds can be compared file by file.
+
+A plain run does only that.  --full adds everything below, as separate measurements after the headline.
+
+Beside `value` a --full run reports, each as the median of its own timed calls:
   value_k10         the same call at K = 10 (SURVEY.md 8d's K) whenever --steps is something else: the cost of an
                     iteration depends on how far the clouds are from their pose, so numbers at different K do not compare
   value_bruteforce  the same K-iteration call with the brute-force kNN kernel in the loop (all n*m
@@ -31,15 +41,17 @@ Beside `value` the same run reports, each as the median of its own timed calls:
 `value_bruteforce_valu` is the same call with the float32 FMA kernel of rounds 1-3.
 
 For N>1 launch with torch.distributed.run (one rank per GPU, weak scaling: 256 clouds per rank).
-Rank 0 prints ONE JSON line.  Kernel times come from HIP events carried on the dispatches of the last
-timed call; `roofline` is the kernel with the LARGEST SHARE of that call (shares are in the line), the
+Rank 0 prints ONE JSON line.  Kernel times (--full) come from HIP events carried on the dispatches of one
+more K-iteration call after the timed ones; `roofline` is the kernel with the LARGEST SHARE of that call (shares are in the line), the
 other two legs ride beside it: the search (`bound: "valu"`: f32 FMA work, 8 flop per scored pair against
 the 157.3 TF f32 peak) and the HBM-bound forward / backward accumulate kernels on their ALGORITHMIC bytes
 (48n / 88n per cloud; 44n / 84n when the weights are the implicit ones and nothing is read
 for them).  `cpu_baseline` is the CPU oracle (the reference's op sequence) timed on this host for a
-bounded sample.  The gate compares the TIMED call's own poses and gradients (K iterations, certificates
-engaged) with the oracle run for the same K iterations on the first two clouds; the run FAILS (exit 1 on
-every rank, value null) if a result of any rank is not finite or the pose differs by > 1e-4.
+bounded sample.  The gate (--full) compares the TIMED call's own poses and gradients (K iterations, certificates
+engaged) with the oracle run for the same K iterations on the first two clouds -- for K above GATE_MAX_ITERS, which
+the oracle could not replay in the time a run has, those of a GATE_MAX_ITERS-iteration call of the same configuration
+on the same batch (the line's `check.what` says which); the run FAILS (exit 1 on
+every rank, value null) if a result of any rank is not finite or (--full) the pose differs by > 1e-4.
 """
 import argparse
 import gc
@@ -60,12 +72,15 @@ from dicp_amd.ICP import ICP                            # noqa: E402
 from dicp_amd.synthetic import make_pairs, make_scene_pairs, make_independent_pairs   # noqa: E402
 
 STEADY_CALLS, STEADY_MAX = 3, 40   # untimed K-iteration calls before the timed ones: at least / at most
+STEADY_BUDGET_S = 8.0        # ... and no more once they have taken this long (at least two calls): a plain run's time outside its steps stays bounded at any K
+DUMP_ROWS, DUMP_SEED = 1 << 16, 20240   # --dump-outputs: rows kept of a larger array, and the seed that picks them
 F32_PEAK_TFLOPS = 157.3      # MI355X_MICROARCH.md: f32 vector == f32-input MFMA peak
 F16_MFMA_PEAK_TFLOPS = 2500.0   # ... dense f16 / bf16 MFMA peak
 HBM_PEAK_GBS = 8000.0        # HBM3E spec
 LOSS = {"name": "huber", "metric": 1.0}
 TRIM = 5.0
 POSE_BAR = 1e-4              # north-star parity bar for poses
+GATE_MAX_ITERS = 48          # the oracle replays the gated call on the host's CPU, ~0.4 s per iteration for two 16384-point clouds: ~20 s at most
 GRAD_BAR = 1e-3              # ... and for gradients (of their scale)
 EV_PER_ITER = 6              # dicp_loop_buffers.events: kNN, accumulate (forward), accumulate_bwd -- a start/stop pair each
 
@@ -165,6 +180,28 @@ def run_call(icp, src, tgt, T0, world):
     if work is not None:
         work.wait()
     return out, T_all, s.grad, t.grad
+
+
+def dump_outputs(path, out, T_all, g_src, g_tgt):
+    """--dump-outputs: the timed call's results as path/<name>.npy, float32 (float64 for float64 results and for integer / boolean ones).  Rows are
+    the last dimension when it is at most 16 wide, single elements otherwise; an array of more than DUMP_ROWS rows keeps DUMP_ROWS of them, drawn
+    with a generator seeded DUMP_SEED (the same rows of pc and of the source gradient: arrays of one row count share the draw)."""
+    import numpy as np
+    arrays = {"T": out["T"], "pc": out["pc"], "deltas": out["deltas"], "weights": out["weights"], "costs": out["costs"],
+              "grad_source": g_src, "grad_target": g_tgt}
+    arrays.update({"stats_" + k: v for k, v in out["stats"].items()})
+    if T_all is not None:
+        arrays["T_all"] = T_all                              # (the all-gathered poses of every rank)
+    os.makedirs(path, exist_ok=True)
+    for name, x in arrays.items():
+        x = x.detach()
+        rows = x.reshape(-1, x.shape[-1]) if x.dim() and x.shape[-1] <= 16 else x.reshape(-1, 1)
+        if rows.shape[0] > DUMP_ROWS:
+            pick = torch.randint(0, rows.shape[0], (DUMP_ROWS,), generator=torch.Generator().manual_seed(DUMP_SEED)).sort().values
+            x = rows[pick.to(rows.device)]
+        x = x.cpu()
+        x = x.double() if x.dtype == torch.float64 or not x.is_floating_point() else x.float()
+        np.save(os.path.join(path, name + ".npy"), x.numpy())
 
 
 _T_START = time.perf_counter()
@@ -314,8 +351,8 @@ def other_configs(make_icp, dev, sync):
     return out
 
 
-def oracle_gate(src, tgt, K, out_T, g_src, g_tgt):
-    """The TIMED call's own results on its first clouds against the oracle run for the same K iterations (fwd+bwd):
+def oracle_gate(src, tgt, K, out_T, g_src, g_tgt, call="the timed call's own"):
+    """A call's results (the TIMED call's own unless `call` says otherwise) on its first clouds against the oracle run for the same K iterations (fwd+bwd):
     -> (dict for the line, ok).  Pose bar 1e-4; gradients: median row error <= 1e-5 and at most 0.1 % of the rows beyond 1e-3
     of the gradient's scale (a float32 argmin may pick the other of two nearly equidistant targets for a handful of queries)."""
     from oracle import dicp_oracle as O
@@ -327,7 +364,7 @@ def oracle_gate(src, tgt, K, out_T, g_src, g_tgt):
     ref["T"].sum().backward()
     dT = float((out_T.detach().cpu() - ref["T"].detach()).abs().max())
     info = {"pose_max_abs_diff_vs_oracle": dT, "bar": POSE_BAR, "clouds": Bc, "iterations": K,
-            "what": "the timed call's own T / source.grad / target.grad (clouds 0..%d) against the oracle run for the same %d iterations" % (Bc - 1, K),
+            "what": "%s T / source.grad / target.grad (clouds 0..%d) against the oracle run for the same %d iterations" % (call, Bc - 1, K),
             "oracle_seconds": None}
     ok = dT <= POSE_BAR
     for name, got, want in (("source", g_src, s.grad), ("target", g_tgt, t.grad)):
@@ -349,13 +386,16 @@ def main(argv=None, make_icp=None, device=None, backend="nccl", emit=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10, help="K: ICP iterations per timed call (SURVEY 8d: 10)")
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--reps", type=int, default=5, help="timed K-iteration calls; `value` is their median (>= 5)")
+    ap.add_argument("--reps", type=int, default=1, help="timed K-iteration calls; `value` is their median (default 1: the timed steps are exactly --steps)")
     ap.add_argument("--batch", type=int, default=256, help="clouds per GPU")
     ap.add_argument("--points", type=int, default=16384, help="points per cloud (source and target)")
     ap.add_argument("--knn", choices=["auto", "sweep", "valu", "mfma"], default="auto",
                     help="auto/sweep: exact slab-pruned kNN (same indices as brute force); valu/mfma: brute-force kernels")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra-legs", action="store_true", help="skip value_k10 / value_bruteforce / value_tolerance / value_structured")
+    ap.add_argument("--full", action="store_true", help="after the headline also measure and check everything else: the other legs and configs, "
+                                                         "the roofline's kernel timings, the pose all-gather, the CPU baseline and the oracle gate")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed call's results to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the oracle gate")
+    ap.add_argument("--no-extra-legs", action="store_true", help="with --full: skip value_k10 / value_bruteforce / value_tolerance / value_structured / ...")
     args = ap.parse_args(argv)
     head = git_head()                   # (a subprocess: before the GPU or the process group is touched)
     on_gpu = device is None
@@ -404,7 +444,9 @@ def main(argv=None, make_icp=None, device=None, backend="nccl", emit=None):
             raise SystemExit("bench.py --gpus %d: the ranks map to devices %s -- one rank per device is required" % (args.gpus, seen_devices))
 
     B, n, m, K, W = args.batch, args.points, args.points, args.steps, args.warmup
-    reps = max(5, args.reps)
+    reps = max(1, args.reps)                # the timed calls of the headline: reps x K timed steps
+    leg_reps = max(5, args.reps)            # --full: the timed calls of each other leg
+    torch.manual_seed(0)                    # (the inputs are seeded by make_pairs itself; this pins whatever else draws from the global generator)
     src, tgt = make_pairs(B, n, m, seed=3, dtype=torch.float32, first=rank * B)
     src, tgt = src.to(dev), tgt.to(dev)
     T0 = torch.eye(4, device=dev).repeat(B, 1, 1)
@@ -435,16 +477,18 @@ def main(argv=None, make_icp=None, device=None, backend="nccl", emit=None):
     def steady(icp_obj, data, least=STEADY_CALLS, most=STEADY_MAX):
         """Untimed calls at the timed call's own shapes until three in a row agree to 3 %: the caching allocator then owns
         the K-sized buffers (the first use of a new size is a synchronous hipMalloc) and the chip is in its steady state
-        (back-to-back calls get faster for a while on a cold box: scripts/call_repeat_diag.py).  Same count on every rank."""
-        calls, recent, held = 0, [], None
+        (back-to-back calls get faster for a while on a cold box: scripts/call_repeat_diag.py), or until they have taken STEADY_BUDGET_S.  Same count on
+        every rank."""
+        calls, recent, held, spent = 0, [], None, 0.0
         while calls < most:
             sync()
             t_w = time.perf_counter()
             held = run_call(icp_obj, data[0], data[1], T0, cw)      # (the previous call's results stay alive during the next one, as in timed(): the
             sync()                                                  #  allocator then owns room for two result sets before the first timed call)
             recent = (recent + [time.perf_counter() - t_w])[-3:]
+            spent += recent[-1]
             calls += 1
-            done = calls >= least and max(recent) <= 1.03 * min(recent)
+            done = (calls >= least and max(recent) <= 1.03 * min(recent)) or (calls >= 2 and spent >= STEADY_BUDGET_S)
             if use_dist:
                 flag = torch.tensor([1 if done else 0], device=dev)
                 torch.distributed.all_reduce(flag, op=torch.distributed.ReduceOp.MIN)
@@ -458,7 +502,7 @@ def main(argv=None, make_icp=None, device=None, backend="nccl", emit=None):
         """`count` calls, each bracketed by barrier + device sync on both sides; per call the MAX over ranks (and every rank's own time)."""
         times, by_rank, last = [], [], None
         for i in range(count):
-            if events is not None:          # the kernel timings of the roofline legs: HIP events on the dispatches of the LAST timed call only
+            if events is not None:          # the kernel timings of the roofline legs: HIP events on the dispatches of the LAST call only
                 icp_obj._tuning["timing_events"] = events if i == count - 1 else None
             fence()
             t0 = time.perf_counter()
@@ -482,11 +526,11 @@ def main(argv=None, make_icp=None, device=None, backend="nccl", emit=None):
         run_call(icp, src, tgt, T0, cw)                                  # W untimed warm-up steps
     icp.max_iterations = K
     log = EventLog()
-    if on_gpu:
-        log.handles(K)                      # create the HIP events now: not part of the timed workload
     # An event pair carried on a dispatch costs the queue ~4 us of idle time before the next dependent launch (6 % of a call at this shape:
-    # profiles/r02_timed_call_timeline*.txt): the events ride on the last timed call only, `value` is the median of all of them.
-    use_events = on_gpu and os.environ.get("DICP_BENCH_NO_EVENTS") != "1"
+    # profiles/r02_timed_call_timeline*.txt): the events ride on one more call after the timed ones (--full), never on a timed call.
+    use_events = args.full and on_gpu and os.environ.get("DICP_BENCH_NO_EVENTS") != "1"
+    if use_events:
+        log.handles(K)                      # create the HIP events now: not part of the timed workload
     icp._tuning["timing_events"] = None
     # a generational GC pass over this process's heap takes tens of ms (10 steps take 5 ms): whether one lands inside a
     # timed call depends on the allocation count so far, i.e. on things as irrelevant as argv -> collect now and pause
@@ -495,11 +539,72 @@ def main(argv=None, make_icp=None, device=None, backend="nccl", emit=None):
     gc.collect()
     gc.disable()
     steady_calls = steady(icp, data)
-    times, (out, T_all, gs, gt), by_rank = timed(icp, data, reps, log if use_events else None)      # reps x exactly K steps
+    times, (out, T_all, gs, gt), by_rank = timed(icp, data, reps)      # reps x exactly K steps
     elapsed = median(times)
     i_med = sorted(range(len(times)), key=lambda i: times[i])[len(times) // 2]
-    ev_ms = {nm: (log.all_ms(nm) if on_gpu else []) for nm in ("knn", "accumulate", "accumulate_bwd")}       # of the LAST timed call
     sane = bool(torch.isfinite(out["T"]).all() and torch.isfinite(gs).all() and torch.isfinite(gt).all())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, T_all if use_dist else None, gs, gt)
+    progress("timed calls done (K = %d): %.3f ms per call" % (K, elapsed * 1e3))
+    line = {
+        "metric": "ICP cloud-iterations/sec (fwd+bwd), B=%dx%d-pt clouds per GPU" % (B, n),
+        "value": world * B * K / elapsed,
+        "unit": "cloud-iterations/s",
+        "n_gpus": world, "steps": K, "warmup": W,
+        "timed_calls": reps, "call_ms": [round(v * 1e3, 4) for v in times],
+        "call_ms_by_rank": [round(v * 1e3, 4) for v in by_rank[i_med]],
+        "pose_allgather_ms": None,
+        "value_note": "median of %d timed %d-iteration calls (each: barrier + sync, icp() + backward(), barrier + sync; max over ranks; call_ms_by_rank: every "
+                      "rank's own time of the median call)" % (reps, K),
+        "warmup_note": "W-iteration call, then %d untimed K-iteration calls (until three in a row agree to 3 %%, or %.0f s of them: allocator + steady state at "
+                       "the timed shapes)" % (steady_calls, STEADY_BUDGET_S),
+        "ms_per_step": elapsed * 1e3 / K,
+        "batch_iterations_per_s": K / elapsed,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32", "data": "synthetic",
+        "ranks_seen": ranks_seen, "rccl_version": rccl, "head": head,
+        "config": {"workload": "BASELINE configs[2]: B=%d/GPU synthetic %d-pt clouds, point-to-plane + huber(1.0) + "
+                               "trim(5.0), differentiable, dim=3, K=%d const iterations fwd + backward of T.sum() "
+                               "w.r.t. source and target" % (B, n, K),
+                   "K": K, "clouds_per_gpu": B, "points": n, "icp_type": "pt2pl", "knn": args.knn,
+                   "parallelism": "batch-sharded x%d, one pose all-gather per call" % world},
+    }
+
+    def finish(sane):
+        """`finite` on every rank (and, --full, the oracle gate of rank 0) decides the exit status and whether the line may carry a value."""
+        if use_dist:
+            flag = torch.tensor([1 if sane else 0], device=dev)
+            torch.distributed.all_reduce(flag, op=torch.distributed.ReduceOp.MIN)
+            sane = bool(flag.item())
+        if rank == 0:
+            line["finite"] = sane
+            if not sane:        # a wrong-result kernel must not emit a headline number
+                line["invalid_value"] = line["value"]
+                line["value"] = None
+                line["error"] = ("results not finite on some rank, or the timed call differs from the oracle (pose bar %g, gradient bar %g)" % (POSE_BAR, GRAD_BAR)
+                                 if args.full else "results not finite on some rank")
+            (emit or (lambda text: os.write(_REAL_STDOUT, text.encode())))(json.dumps(line) + "\n")
+        if use_dist:
+            torch.distributed.destroy_process_group()
+        return 0 if sane else 1
+
+    if not args.full:
+        gc.enable()
+        line["config"]["k_note"] = ("value is cloud-iterations/s at K = %d constant iterations, of which ~%d run after the clouds have converged; bench.py --full "
+                                    "reports the same run at K = 10, in tolerance mode and on independently sampled clouds beside it" % (K, max(0, K - 6)))
+        return finish(sane)
+
+    # ---- --full: everything beyond the headline, after it.  Of the timed call's results the rest needs only the poses and the first two clouds'
+    # gradients (the gate): the K-sized ones go now, before the legs allocate their own
+    T_timed, gate_gs, gate_gt = out["T"].detach(), gs[:2].detach(), gt[:2].detach()
+    del out, T_all, gs, gt
+    ev_ms = {nm: [] for nm in ("knn", "accumulate", "accumulate_bwd")}
+    last_ms = times[-1] * 1e3
+    if use_events:
+        ev_times, _, _ = timed(icp, data, 1, log)       # one more K-iteration call, its dispatches carrying the events
+        icp._tuning["timing_events"] = None
+        last_ms = ev_times[0] * 1e3
+        ev_ms = {nm: log.all_ms(nm) for nm in ev_ms}
     from dicp_amd import _ops, _lib as L
     from dicp_amd._ops import auto_knn_kind
     # knn=auto takes the brute-force kernel for small clouds (no sorted-sweep statistics then)
@@ -522,21 +627,20 @@ def main(argv=None, make_icp=None, device=None, backend="nccl", emit=None):
         return pairs, cert
 
     pairs_scored, certified = sweep_stats(icp, K)
-    # the backward's truncated reverse sweep: clouds at work per iteration of the last timed call (None: feature off / not this path)
+    # the backward's truncated reverse sweep: clouds at work per iteration of the object's last call (None: feature off / not this path)
     bwd_live = icp.knn_stats.get("bwd_live") if on_gpu else None
     bwd_live = [int(v) for v in bwd_live[:K].tolist()] if bwd_live is not None else None
 
     # ---- the other legs, in the same run (each the median of its own timed calls)
-    progress("timed calls done (K = %d): %.3f ms per call" % (K, elapsed * 1e3))
     extra = {}
     if not args.no_extra_legs:
         if K != 10:
             progress("leg: value_k10")
             k10 = new_icp(10)
             steady(k10, data, least=3, most=8)
-            kt, _, _ = timed(k10, data, reps)
+            kt, _, _ = timed(k10, data, leg_reps)
             extra["value_k10"] = world * B * 10 / median(kt)
-            extra["k10_note"] = "the same call at K = 10 (SURVEY.md 8d): %.3f ms per step, median of %d calls" % (median(kt) * 1e3 / 10, reps)
+            extra["k10_note"] = "the same call at K = 10 (SURVEY.md 8d): %.3f ms per step, median of %d calls" % (median(kt) * 1e3 / 10, leg_reps)
             del k10
         # A training loop presents NEW clouds of the same shape every step, and what an ICP object carries from call to call (CallHints: tail placement,
         # certificate pauses, the scoring forms' plan) was learned on other data.  The K = 10 call of ONE object rotating over four different batches
@@ -570,7 +674,7 @@ def main(argv=None, make_icp=None, device=None, backend="nccl", emit=None):
             for _ in range(3):
                 gout, ggr = gstep(gs_, gt_, T0)
             gtimes = []
-            for _ in range(reps):
+            for _ in range(leg_reps):
                 fence()
                 t0_ = time.perf_counter()
                 gout, ggr = gstep(gs_, gt_, T0)
@@ -595,11 +699,11 @@ def main(argv=None, make_icp=None, device=None, backend="nccl", emit=None):
         progress("leg: value_tolerance")
         tol = new_icp(50, tol=1e-4, const_iter=False)
         steady(tol, data, least=3, most=8)
-        tt, (tout, _, _, _), _ = timed(tol, data, reps)
+        tt, (tout, _, _, _), _ = timed(tol, data, leg_reps)
         k_exec = int(tout["deltas"].shape[1])
         extra["value_tolerance"] = world * B * k_exec / median(tt)
         extra["tolerance_note"] = ("tolerance 1e-4, max 50 iterations, const_iter off: %d iterations executed, %.3f ms per call, "
-                                   "median of %d calls" % (k_exec, median(tt) * 1e3, reps))
+                                   "median of %d calls" % (k_exec, median(tt) * 1e3, leg_reps))
         del tol, tout
         # LiDAR-like scenes: planar structure, two walls perpendicular to the sweep's sort axis
         progress("leg: value_structured")
@@ -607,13 +711,13 @@ def main(argv=None, make_icp=None, device=None, backend="nccl", emit=None):
         scene = (s2.to(dev), t2.to(dev))
         sc = new_icp(K)
         steady(sc, scene, least=3, most=8)
-        st_, (sout, _, sgs, sgt), _ = timed(sc, scene, reps)
+        st_, (sout, _, sgs, sgt), _ = timed(sc, scene, leg_reps)
         sp, _ = sweep_stats(sc, K)
         extra["value_structured"] = world * B * K / median(st_)
         extra["structured_note"] = ("the same %d-iteration call on make_scene_pairs (ground plane 40 %%, four walls 12.5 %% each -- two of them perpendicular to x --, "
                                     "10 %% clutter; the search frame picks an oblique sort direction there, and the clouds' match certificates switch themselves off: "
                                     "8 %% of the queries sit within float32 rounding of a second candidate on the dense surfaces): %.3f ms per step, median of %d calls%s; finite: %s"
-                                    % (K, median(st_) * 1e3 / K, reps, "" if sp is None else ", pairs scored %.2f %% of n*m per launch" % (100.0 * sp / (float(n) * m * B)),
+                                    % (K, median(st_) * 1e3 / K, leg_reps, "" if sp is None else ", pairs scored %.2f %% of n*m per launch" % (100.0 * sp / (float(n) * m * B)),
                                        bool(torch.isfinite(sout["T"]).all() and torch.isfinite(sgs).all() and torch.isfinite(sgt).all())))
         if sp is not None:
             extra["structured_pairs_scored_fraction"] = sp / (float(n) * m * B)
@@ -702,7 +806,7 @@ def main(argv=None, make_icp=None, device=None, backend="nccl", emit=None):
         for _ in range(5):
             fence()
             t0 = time.perf_counter()
-            _, work = ddist.gather_poses_async(out["T"].detach(), total=B * abs(cw), force=True)
+            _, work = ddist.gather_poses_async(T_timed, total=B * abs(cw), force=True)
             if work is not None:
                 work.wait()
             sync()
@@ -737,13 +841,15 @@ def main(argv=None, make_icp=None, device=None, backend="nccl", emit=None):
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         progress("cpu baseline (bounded sample) and oracle gate")
         base = cpu_baseline(n, m)
-        gate, ok = oracle_gate(src[:2], tgt[:2], K, out["T"][:2], gs[:2], gt[:2])
+        if K <= GATE_MAX_ITERS:
+            gate, ok = oracle_gate(src[:2], tgt[:2], K, T_timed[:2], gate_gs, gate_gt)
+        else:       # (the oracle's cost grows with K: a shorter call of the same configuration, on the same batch, is held to it instead)
+            g_out, _, g_s, g_t = run_call(new_icp(GATE_MAX_ITERS), src, tgt, T0, cw)
+            gate, ok = oracle_gate(src[:2], tgt[:2], GATE_MAX_ITERS, g_out["T"][:2], g_s[:2], g_t[:2],
+                                   call="a %d-iteration call of the timed configuration on the same batch (the timed call's K = %d is beyond what the oracle "
+                                        "replays in a run's time)" % (GATE_MAX_ITERS, K))
+            del g_out, g_s, g_t
         sane = sane and ok
-    if use_dist:
-        flag = torch.tensor([1 if sane else 0], device=dev)
-        torch.distributed.all_reduce(flag, op=torch.distributed.ReduceOp.MIN)
-        sane = bool(flag.item())
-    rc = 0 if sane else 1
 
     if rank == 0:
         def mean(v):
@@ -765,8 +871,7 @@ def main(argv=None, make_icp=None, device=None, backend="nccl", emit=None):
         acc_traffic, acc_src = pmc_traffic("accumulate_kernel", B, n)
         bf_traffic, bf_src = pmc_traffic("knn_valu", B, n)
         bfm_traffic, bfm_src = pmc_traffic("knn_f16_kernel", B, n)
-        last_ms = times[-1] * 1e3                                        # the call that carried the events
-        share = {nm: (sum(v) / last_ms if v else 0.0) for nm, v in ev_ms.items()}
+        share ={nm: (sum(v) / last_ms if v else 0.0) for nm, v in ev_ms.items()}
         # which scoring form each iteration's search took: the plan the object's earlier calls of this shape left (dicp_loop_buffers.search.form_plan; 0 = the default
         # by size, the matrix cores from 16384 targets on), the certifying search and the guard launches are vector code
         forms = None
@@ -823,37 +928,19 @@ def main(argv=None, make_icp=None, device=None, backend="nccl", emit=None):
             legs[nm]["share_of_timed_call"] = round(share[nm], 4)
             legs[nm]["total_ms_in_call"] = round(sum(ev_ms[nm]), 4) if ev_ms[nm] else None
         top = max(share, key=lambda nm: share[nm]) if any(share.values()) else "knn"
-        line = {
-            "metric": "ICP cloud-iterations/sec (fwd+bwd), B=%dx%d-pt clouds per GPU" % (B, n),
-            "value": world * B * K / elapsed,
-            "unit": "cloud-iterations/s",
-            "n_gpus": world, "steps": K, "warmup": W,
-            "timed_calls": reps, "call_ms": [round(v * 1e3, 4) for v in times],
-            "call_ms_by_rank": [round(v * 1e3, 4) for v in by_rank[i_med]],
-            "pose_allgather_ms": gather_ms,
-            "value_note": "median of %d timed %d-iteration calls (each: barrier + sync, icp() + backward(), barrier + sync; max over ranks; call_ms_by_rank: every "
-                          "rank's own time of the median call); the last of them carries the HIP events of the roofline legs on its dispatches "
-                          "(~6 %% slower for it: an event pair costs the queue ~4 us)" % (reps, K),
-            "warmup_note": "W-iteration call, then %d untimed K-iteration calls (until three in a row agree to 3 %%: allocator + steady state at the timed shapes)" % steady_calls,
-            "ms_per_step": elapsed * 1e3 / K,
-            "batch_iterations_per_s": K / elapsed,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
-            "ranks_seen": ranks_seen, "rccl_version": rccl, "head": head,
-            "config": {"workload": "BASELINE configs[2]: B=%d/GPU synthetic %d-pt clouds, point-to-plane + huber(1.0) + "
-                                   "trim(5.0), differentiable, dim=3, K=%d const iterations fwd + backward of T.sum() "
-                                   "w.r.t. source and target" % (B, n, K),
-                       "K": K, "clouds_per_gpu": B, "points": n, "icp_type": "pt2pl", "knn": args.knn,
-                       "parallelism": "batch-sharded x%d, one pose all-gather per call" % world,
-                       # (`value` grows with K -- the clouds converge in ~6 iterations, every further one is a certified iteration that costs a
-                       #  sixth of an early one; the same run's other figures belong next to it wherever it is quoted)
-                       "k_note": ("value is cloud-iterations/s at K = %d constant iterations, of which ~%d run after the clouds have converged; the same run at SURVEY 8d's "
-                                  "K = 10: value_k10 = %s; in the reference's default tolerance mode (const_iter off, 6 iterations executed): value_tolerance = %s; on "
-                                  "independently sampled, partially overlapping clouds with metre-sized start poses (K = 10): value_independent = %s"
-                                  % (K, max(0, K - 6), ("%.0f" % extra["value_k10"]) if "value_k10" in extra else ("%.0f" % (world * B * K / elapsed) if K == 10 else "not run"),
-                                     ("%.0f" % extra["value_tolerance"]) if "value_tolerance" in extra else "not run",
-                                     ("%.0f" % extra["value_independent"]) if "value_independent" in extra else "not run"))},
-            "roofline": dict(legs[top], dominant="largest share of the event-carrying timed call (%.3f ms): %s"
+        line["pose_allgather_ms"] = gather_ms
+        if use_events:
+            line["value_note"] += "; the roofline legs' HIP events ride on one more call after them (an event pair costs the queue ~4 us)"
+        # (`value` grows with K -- the clouds converge in ~6 iterations, every further one is a certified iteration that costs a
+        #  sixth of an early one; the same run's other figures belong next to it wherever it is quoted)
+        line["config"]["k_note"] = ("value is cloud-iterations/s at K = %d constant iterations, of which ~%d run after the clouds have converged; the same run at SURVEY 8d's "
+                                    "K = 10: value_k10 = %s; in the reference's default tolerance mode (const_iter off, 6 iterations executed): value_tolerance = %s; on "
+                                    "independently sampled, partially overlapping clouds with metre-sized start poses (K = 10): value_independent = %s"
+                                    % (K, max(0, K - 6), ("%.0f" % extra["value_k10"]) if "value_k10" in extra else ("%.0f" % (world * B * K / elapsed) if K == 10 else "not run"),
+                                       ("%.0f" % extra["value_tolerance"]) if "value_tolerance" in extra else "not run",
+                                       ("%.0f" % extra["value_independent"]) if "value_independent" in extra else "not run"))
+        line.update({
+            "roofline": dict(legs[top], dominant="largest share of the event-carrying call (%.3f ms): %s"
                              % (last_ms, ", ".join("%s %.0f %%" % (nm, 100 * share[nm]) for nm in sorted(share, key=lambda q: -share[q])))),
             "roofline_bruteforce_knn": {"kernel": "knn_valu_kernel (all n*m pairs, float32 FMA)", "bound": "valu",
                                         "achieved": flops_bf / (bf_ms * 1e-3) / 1e12 if bf_ms else None, "peak": F32_PEAK_TFLOPS, "unit": "TFLOP/s",
@@ -874,15 +961,14 @@ def main(argv=None, make_icp=None, device=None, backend="nccl", emit=None):
                               "instructions) -- and by the clock the chip holds under it (1.7 GHz); matrix-pipe busy 48 % of the kernel here, 56 % at 256 x 65536 "
                               "(SQ_VALU_MFMA_BUSY_CYCLES, profiles/r04_knn_f16_c3_pmc.txt, profiles/r04_knn_c4_65536_pmc.txt)",
                 "measured": "3 extra launches outside the timed region, HIP events"},
-            "finite": sane,
-        }
+        })
         if ev_ms["knn"] and ev_ms["accumulate"] and not brute:
             cf = max(k for k in (getattr(icp, "_tuning", {}).get("sweep_resort") or (0, 1, 2, 3)) if k < K) if certified is not None else K
             classes = {"full_search": list(range(0, min(cf, K))), "certifying_search": [cf] if cf < K else [], "certified": list(range(cf + 1, K))}
             line["ms_by_iteration_class"] = {
                 nm: {"iterations": ks, "search_ms_mean": round(sum(ev_ms["knn"][k] for k in ks) / len(ks), 4),
                      "accumulate_ms_mean": round(sum(ev_ms["accumulate"][k] for k in ks) / len(ks), 4)} for nm, ks in classes.items() if ks}
-            line["ms_by_iteration_class"]["note"] = ("HIP events of the last timed call; certified: the search launch is the guard (it works through the list of units the "
+            line["ms_by_iteration_class"]["note"] = ("HIP events of the event-carrying call; certified: the search launch is the guard (it works through the list of units the "
                                                      "previous step made: re-searches units with many spent budgets, single queries, re-scores candidate sets), the "
                                                      "accumulate streams each query's cached match row")
         for nm, key in (("knn", "roofline_knn"), ("accumulate", "roofline_accumulate"), ("accumulate_bwd", "roofline_streaming")):
@@ -893,14 +979,7 @@ def main(argv=None, make_icp=None, device=None, backend="nccl", emit=None):
             line["cpu_baseline"] = base
             line["check"] = gate
             line["speedup_vs_cpu"] = line["value"] / base["value"]
-        if not sane:        # a wrong-result kernel must not emit a headline number
-            line["invalid_value"] = line["value"]
-            line["value"] = None
-            line["error"] = "results not finite on some rank, or the timed call differs from the oracle (pose bar %g, gradient bar %g)" % (POSE_BAR, GRAD_BAR)
-        (emit or (lambda text: os.write(_REAL_STDOUT, text.encode())))(json.dumps(line) + "\n")
-    if use_dist:
-        torch.distributed.destroy_process_group()
-    return rc
+    return finish(sane)
 
 
 if __name__ == "__main__":

@@ -1,6 +1,6 @@
 """Timeline of the LAST (timed) ICP call in a rocprofv3 --kernel-trace of bench.py: kernel, duration, gap before it.
 
-    rocprofv3 --kernel-trace -d out -o t --output-format csv -- python3 bench.py --no-cpu-baseline
+    rocprofv3 --kernel-trace -d out -o t --output-format csv -- python3 bench.py --full --no-cpu-baseline
     python scripts/trace_timeline.py out/t_kernel_trace.csv [--full]
 """
 import csv, sys, collections

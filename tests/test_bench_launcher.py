@@ -52,7 +52,7 @@ def worker(rank, world, port, out_dir):
     bench.run_call = counted_call
     lines = []
     rc = bench.main(["--gpus", str(world), "--steps", str(K), "--warmup", "1", "--batch", str(B), "--points", str(N_PTS), "--reps", "5",
-                     "--no-cpu-baseline", "--no-extra-legs"],
+                     "--full", "--no-cpu-baseline", "--no-extra-legs"],
                     make_icp=lambda **kw: OracleICP(out_dir, **kw), device=torch.device("cpu"), backend="gloo", emit=lines.append)
     assert rc == 0
     assert calls and set(calls) == {1}, calls                       # ONE pose all-gather per icp() + backward(), nothing else on the data path
