@@ -1,0 +1,355 @@
+// Surface normals of point clouds (dicp_amd/normals.py): exact k nearest neighbours of every point within its own cloud,
+// a covariance, its smallest eigenvector -- and the gradient of all that back to the points, for targets a network produces.
+//
+// Forward (dicp_normals_forward), all in the SORTED order of the existing sweep set-up:
+//   pack     the xyz columns of (N,m,c) rows into (N,m,3)
+//   sort     dicp_sweep_sort + dicp_sweep_build with frame = NULL: slot s of a cloud holds row tperm[s], ascending in raw x, the axes
+//            as given -- so every distance below is the one the brute-force definition computes, bit for bit
+//   walk     one lane per slot walks outward from its own slot with two cursors, the side with the smaller x gap first, and stops a
+//            side once gap*gap > the k-th best d2 so far.  Exact: d2 = (xx + yy) + zz >= fl(dx*dx) = fl(gap*gap) for sums of
+//            non-negative terms under round-to-nearest, and every row further out on that side has a larger gap.  Ties at the k-th
+//            d2 are still examined, so the (d2, index) order holds.  The top-k list is a sorted register array, its insertion
+//            unrolled; the block's slots +- WALK_HALO rows are staged in LDS.
+//   normals  one lane per slot: the two-pass covariance of its neighbours, svd3, orientation, curvature (csrc/dicp_normals.h).
+// Backward (dicp_normals_backward): one lane per slot recomputes its eigen-system from the saved neighbour slots and adds
+// (2/k_eff) G (q_j - mu) to each neighbour j: into an LDS window of the block's slots +- BWD_HALO rows with LDS atomics, outside
+// it into the sorted gradient rows with global atomics; the window is then flushed as contiguous rows, and one
+// dicp_permute_add_rows returns the rows to the original order.  Float atomics: not bit-reproducible from run to run.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "dicp_common.h"
+#include "dicp_fill.h"
+#include "dicp_normals.h"
+
+namespace {
+
+constexpr int NRM_KMAX = 32;
+template <typename T> struct WalkHalo;                  // LDS rows staged on either side of a block's slots: 36 KiB float4 / 40 KiB double4
+template <> struct WalkHalo<float>  { static constexpr int v = 1024; };
+template <> struct WalkHalo<double> { static constexpr int v = 512; };
+template <typename T> struct BwdHalo;                   // gradient window rows on either side: 27 KiB float / 30 KiB double
+template <> struct BwdHalo<float>  { static constexpr int v = 1024; };
+template <> struct BwdHalo<double> { static constexpr int v = 512; };
+template <typename T> struct NrmTau;
+template <> struct NrmTau<float>  { static constexpr double v = 1e-6; };
+template <> struct NrmTau<double> { static constexpr double v = 1e-12; };
+
+inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// The forward workspace, in this order (each part 256-byte aligned); the backward reads tperm / tgs4 / nbr_s of it
+struct NrmLayout {
+    size_t xyz, keys, tperm, tgs4, nbr_s, scratch, scratch_bytes, total;
+};
+inline NrmLayout nrm_layout(int dtype, int N, int m, int k) {
+    NrmLayout L;
+    const size_t ts = dtype == DICP_F32 ? 4 : 8, m_pad = (size_t)dicp_padded_targets(m);
+    size_t off = 0;
+    L.xyz = off;     off = up256(off + (size_t)N * m * 3 * ts);
+    L.keys = off;    off = up256(off + (size_t)N * m_pad * ts);
+    L.tperm = off;   off = up256(off + (size_t)N * m_pad * 4);
+    L.tgs4 = off;    off = up256(off + (size_t)N * m_pad * 4 * ts);
+    L.nbr_s = off;   off = up256(off + (size_t)N * m_pad * k * 4);
+    L.scratch_bytes = dicp_sweep_sort_scratch_bytes(dtype, N, (int)m_pad);
+    L.scratch = off; off = up256(off + L.scratch_bytes);
+    L.total = off;
+    return L;
+}
+
+// ------------------------------------------------------------------ pack
+template <typename T>
+__global__ __launch_bounds__(BLOCK) void normals_pack_kernel(const T* __restrict__ pts, int c, size_t rows_total, T* __restrict__ xyz) {
+    const size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= rows_total) return;
+    const T* p = pts + i * c;
+    T* o = xyz + i * 3;
+    o[0] = p[0]; o[1] = p[1]; o[2] = p[2];
+}
+
+// ------------------------------------------------------------------ walk
+// (d2, index) order; the list's unused head is -inf (never beaten), its empty tail +inf with index -1
+template <typename T>
+__device__ __forceinline__ bool nrm_before(T da, int ia, T db, int ib) { return da < db || (da == db && ia < ib); }
+
+template <typename T, int K>
+__global__ __launch_bounds__(BLOCK) void normals_knn_kernel(const typename V4<T>::type* __restrict__ tgs4, const int32_t* __restrict__ tperm,
+                                                            const int32_t* __restrict__ rows, int N, int m, int m_pad, int k, int bpc,
+                                                            int32_t* __restrict__ nbr_s, int64_t* __restrict__ nbr_out,
+                                                            unsigned long long* __restrict__ walked) {
+    using T4 = typename V4<T>::type;
+    constexpr int H = WalkHalo<T>::v;
+    __shared__ T4 win[BLOCK + 2 * H];
+    int b, blk;
+    if (!decode_block(bpc, N, b, blk)) return;
+    const int mb = rows_of(rows, b, m);
+    const int s0 = blk * BLOCK, s = s0 + threadIdx.x;
+    const size_t base = (size_t)b * m_pad;
+    if (s0 >= m) return;                                    // (block-uniform)
+    const int wlo = max(s0 - H, 0), whi = min(s0 + BLOCK + H, mb);
+    for (int r = threadIdx.x; r < whi - wlo; r += BLOCK) win[r] = tgs4[base + wlo + r];
+    __syncthreads();
+    const bool live = s < mb;
+    unsigned long long steps = 0;
+    if (live) {
+        auto row = [&](int j) -> T4 { return (j >= wlo && j < whi) ? win[j - wlo] : tgs4[base + j]; };
+        T d[K];
+        int id[K], sl[K];
+#pragma unroll
+        for (int i = 0; i < K; ++i) { d[i] = i < K - k ? -inf_v<T>() : inf_v<T>(); id[i] = -1; sl[i] = -1; }
+        const T4 p = row(s);
+        auto consider = [&](const T4& y, int j) {
+            const T dx = y.x - p.x;
+            const T dy = y.y - p.y;
+            const T dz = y.z - p.z;
+            const T xx = dx * dx;
+            const T yy = dy * dy;
+            const T zz = dz * dz;
+            const T d2 = (xx + yy) + zz;
+            if (!(d2 <= d[K - 1])) return;
+            const int o = tperm[base + j];
+            if (!nrm_before(d2, o, d[K - 1], id[K - 1])) return;
+#pragma unroll
+            for (int i = K - 1; i > 0; --i) {
+                const bool shift = nrm_before(d2, o, d[i - 1], id[i - 1]);
+                const bool put = !shift && (i == K - 1 || nrm_before(d2, o, d[i], id[i]));
+                d[i] = shift ? d[i - 1] : (put ? d2 : d[i]);
+                id[i] = shift ? id[i - 1] : (put ? o : id[i]);
+                sl[i] = shift ? sl[i - 1] : (put ? j : sl[i]);
+            }
+            if (nrm_before(d2, o, d[0], id[0])) { d[0] = d2; id[0] = o; sl[0] = j; }
+        };
+        consider(p, s);
+        int lo = s - 1, hi = s + 1;
+        bool cl = lo >= 0, ch = hi < mb;
+        T4 yl = row(cl ? lo : s), yh = row(ch ? hi : s);
+        while (cl || ch) {
+            const T gl = p.x - yl.x, gh = yh.x - p.x;
+            const bool left = cl && (!ch || gl <= gh);
+            const T g = left ? gl : gh;
+            const T g2 = g * g;
+            if (g2 > d[K - 1]) break;                       // this side is the nearer one: the other is beyond the bound as well
+            ++steps;
+            if (left) { consider(yl, lo); --lo; cl = lo >= 0; if (cl) yl = row(lo); }
+            else      { consider(yh, hi); ++hi; ch = hi < mb; if (ch) yh = row(hi); }
+        }
+        const size_t q = base + s;
+        const int orow = tperm[q];
+#pragma unroll
+        for (int i = 0; i < K; ++i) {
+            if (i < K - k) continue;
+            const int o = i - (K - k);
+            nbr_s[q * k + o] = sl[i];
+            if (nbr_out) nbr_out[((size_t)b * m + orow) * k + o] = id[i];
+        }
+    } else if (s < m && nbr_out) {                          // the row s of the cloud's padding (original order)
+        for (int o = 0; o < k; ++o) nbr_out[((size_t)b * m + s) * k + o] = -1;
+    }
+    if (walked) {                                           // diagnostics: rows walked, one atomic per wave
+        unsigned long long t = steps;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) t += __shfl_xor(t, off);
+        if ((threadIdx.x & (WAVE - 1)) == 0 && t) atomicAdd(walked + b, t);
+    }
+}
+
+// ------------------------------------------------------------------ per-point eigen-system (forward and backward)
+struct NrmPoint {
+    double mu[3], lam[3], v[9], s;
+    int k_eff;
+};
+template <typename T>
+__device__ __forceinline__ void nrm_point(const typename V4<T>::type* __restrict__ rows4, const int32_t* __restrict__ nb, int k_eff,
+                                          const typename V4<T>::type& p, const T* __restrict__ vp, NrmPoint& P) {
+    P.k_eff = k_eff;
+    double sum[3] = {0.0, 0.0, 0.0};
+    for (int o = 0; o < k_eff; ++o) {
+        const auto y = rows4[max(nb[o], 0)];      // (-1 only next to rows whose d2 overflows: output unspecified there)
+        sum[0] += (double)y.x - (double)p.x; sum[1] += (double)y.y - (double)p.y; sum[2] += (double)y.z - (double)p.z;
+    }
+    P.mu[0] = sum[0] / k_eff; P.mu[1] = sum[1] / k_eff; P.mu[2] = sum[2] / k_eff;
+    double C6[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int o = 0; o < k_eff; ++o) {
+        const auto y = rows4[max(nb[o], 0)];      // (-1 only next to rows whose d2 overflows: output unspecified there)
+        const double dd[3] = {((double)y.x - (double)p.x) - P.mu[0], ((double)y.y - (double)p.y) - P.mu[1], ((double)y.z - (double)p.z) - P.mu[2]};
+        nrm_cov_add(C6, dd);
+    }
+#pragma unroll
+    for (int e = 0; e < 6; ++e) C6[e] /= k_eff;
+    nrm_eig(C6, P.lam, P.v);
+    const double dv[3] = {(vp ? (double)vp[0] : 0.0) - (double)p.x, (vp ? (double)vp[1] : 0.0) - (double)p.y, (vp ? (double)vp[2] : 0.0) - (double)p.z};
+    P.s = nrm_sign(P.v, dv);
+}
+
+template <typename T>
+__global__ __launch_bounds__(BLOCK) void normals_point_kernel(const typename V4<T>::type* __restrict__ tgs4, const int32_t* __restrict__ tperm,
+                                                              const int32_t* __restrict__ rows, int N, int m, int m_pad, int k, int bpc,
+                                                              const int32_t* __restrict__ nbr_s, const T* __restrict__ vp, int vp_stride,
+                                                              T* __restrict__ nrm, T* __restrict__ curv) {
+    int b, blk;
+    if (!decode_block(bpc, N, b, blk)) return;
+    const int mb = rows_of(rows, b, m);
+    const int s = blk * BLOCK + threadIdx.x;
+    if (s >= m) return;
+    const size_t base = (size_t)b * m_pad;
+    const int k_eff = min(k, mb);
+    const size_t orow = (size_t)b * m + (s < mb ? tperm[base + s] : s);    // the padding's rows: row s itself (original order)
+    T n[3] = {T(0), T(0), T(0)};
+    T cv = T(0);
+    if (s < mb && k_eff >= 3) {
+        NrmPoint P;
+        nrm_point<T>(tgs4 + base, nbr_s + (base + s) * k, k_eff, tgs4[base + s], vp ? vp + (size_t)b * vp_stride : nullptr, P);
+        n[0] = (T)(P.s * P.v[0]); n[1] = (T)(P.s * P.v[1]); n[2] = (T)(P.s * P.v[2]);
+        cv = (T)nrm_curvature(P.lam);
+    }
+    nrm[orow * 3] = n[0]; nrm[orow * 3 + 1] = n[1]; nrm[orow * 3 + 2] = n[2];
+    if (curv) curv[orow] = cv;
+}
+
+// ------------------------------------------------------------------ backward
+template <typename T>
+__global__ __launch_bounds__(BLOCK) void normals_bwd_kernel(const typename V4<T>::type* __restrict__ tgs4, const int32_t* __restrict__ tperm,
+                                                            const int32_t* __restrict__ rows, int N, int m, int m_pad, int k, int bpc,
+                                                            const int32_t* __restrict__ nbr_s, const T* __restrict__ vp, int vp_stride,
+                                                            const T* __restrict__ g_nrm, const T* __restrict__ g_curv, T* __restrict__ gs /* (N,m_pad,3) sorted */) {
+    constexpr int H = BwdHalo<T>::v;
+    __shared__ T acc[(BLOCK + 2 * H) * 3];
+    int b, blk;
+    if (!decode_block(bpc, N, b, blk)) return;
+    const int mb = rows_of(rows, b, m);
+    const int s0 = blk * BLOCK, s = s0 + threadIdx.x;
+    if (s0 >= mb) return;                                   // (block-uniform)
+    const size_t base = (size_t)b * m_pad;
+    const int wlo = max(s0 - H, 0), whi = min(s0 + BLOCK + H, mb), wn = (whi - wlo) * 3;
+    for (int e = threadIdx.x; e < wn; e += BLOCK) acc[e] = T(0);
+    __syncthreads();
+    const int k_eff = min(k, mb);
+    if (s < mb && k_eff >= 3) {
+        const size_t orow = (size_t)b * m + tperm[base + s];
+        double gn[3] = {0.0, 0.0, 0.0};
+        if (g_nrm) { gn[0] = (double)g_nrm[orow * 3]; gn[1] = (double)g_nrm[orow * 3 + 1]; gn[2] = (double)g_nrm[orow * 3 + 2]; }
+        const double gk = g_curv ? (double)g_curv[orow] : 0.0;
+        if (gn[0] != 0.0 || gn[1] != 0.0 || gn[2] != 0.0 || gk != 0.0) {
+            const auto p = tgs4[base + s];
+            const int32_t* nb = nbr_s + (base + s) * k;
+            NrmPoint P;
+            nrm_point<T>(tgs4 + base, nb, k_eff, p, vp ? vp + (size_t)b * vp_stride : nullptr, P);
+            double G6[6];
+            if (nrm_grad_cov(P.lam, P.v, P.s, gn, gk, NrmTau<T>::v, G6)) {
+                for (int o = 0; o < k_eff; ++o) {
+                    const int j = nb[o];
+                    if (j < 0) continue;
+                    const auto y = tgs4[base + j];
+                    const double dd[3] = {((double)y.x - (double)p.x) - P.mu[0], ((double)y.y - (double)p.y) - P.mu[1], ((double)y.z - (double)p.z) - P.mu[2]};
+                    double g[3];
+                    nrm_point_grad(G6, dd, k_eff, g);
+                    if (j >= wlo && j < whi) {
+                        T* a = acc + (j - wlo) * 3;
+                        atomicAdd(a, (T)g[0]); atomicAdd(a + 1, (T)g[1]); atomicAdd(a + 2, (T)g[2]);
+                    } else {                                // outside the window: the sorted rows directly
+                        T* a = gs + (base + j) * 3;
+                        unsafeAtomicAdd(a, (T)g[0]); unsafeAtomicAdd(a + 1, (T)g[1]); unsafeAtomicAdd(a + 2, (T)g[2]);
+                    }
+                }
+            }
+        }
+    }
+    __syncthreads();
+    T* out = gs + (base + wlo) * 3;                         // the window: contiguous rows, which neighbouring blocks' windows overlap
+    for (int e = threadIdx.x; e < wn; e += BLOCK) {
+        const T v = acc[e];
+        if (v != T(0)) unsafeAtomicAdd(out + e, v);
+    }
+}
+
+inline int nrm_kcap(int k) { return k <= 8 ? 8 : (k <= 16 ? 16 : 32); }
+
+int nrm_check(int dtype, int N, int m, int k, int vp_per_cloud) {
+    if (bad_dtype(dtype)) return DICP_ERR_DTYPE;
+    if (N <= 0 || m <= 0 || k < 3 || k > NRM_KMAX || (vp_per_cloud != 0 && vp_per_cloud != 1)) return DICP_ERR_SHAPE;
+    if ((size_t)dicp_padded_targets(m) > 0x7fffffffu / NRM_KMAX) return DICP_ERR_SHAPE;
+    return 0;
+}
+
+}  // namespace
+
+size_t dicp_normals_workspace_bytes(int dtype, int N, int m, int k, int c, int backward) {
+    if (nrm_check(dtype, N, m, k, 0) || c < 3) return 0;
+    const size_t ts = dtype == DICP_F32 ? 4 : 8;
+    if (backward) return up256((size_t)N * dicp_padded_targets(m) * 3 * ts);
+    return nrm_layout(dtype, N, m, k).total;
+}
+
+int dicp_normals_forward(int dtype, const void* pts, int c, const int32_t* rows, int N, int m, int k, const void* viewpoint, int vp_per_cloud,
+                         void* normals, void* curvature, int64_t* neighbors, void* workspace, size_t workspace_bytes,
+                         unsigned long long* walked, void* stream) {
+    if (!pts || !normals || !workspace) return DICP_ERR_NULL;
+    int rc = nrm_check(dtype, N, m, k, vp_per_cloud);
+    if (rc) return rc;
+    if (c < 3) return DICP_ERR_SHAPE;
+    const NrmLayout L = nrm_layout(dtype, N, m, k);
+    if (workspace_bytes < L.total) return DICP_ERR_SHAPE;
+    const size_t ts = dtype == DICP_F32 ? 4 : 8;
+    if ((uintptr_t)workspace % 256 || (uintptr_t)pts % ts || (uintptr_t)normals % ts || (curvature && (uintptr_t)curvature % ts) ||
+        (neighbors && (uintptr_t)neighbors % 8) || (viewpoint && (uintptr_t)viewpoint % ts)) return DICP_ERR_ALIGN;
+    hipStream_t st = (hipStream_t)stream;
+    char* ws = (char*)workspace;
+    const int m_pad = dicp_padded_targets(m);
+    void* xyz = ws + L.xyz;
+    int32_t* tperm = (int32_t*)(ws + L.tperm);
+    int32_t* nbr_s = (int32_t*)(ws + L.nbr_s);
+    if (walked && (rc = dicp_fill::zero(walked, (size_t)N * sizeof(unsigned long long), st))) return rc;
+    const size_t rows_total = (size_t)N * m;
+    const unsigned gp = (unsigned)((rows_total + BLOCK - 1) / BLOCK);
+    begin_launch();
+    if (dtype == DICP_F32) normals_pack_kernel<float><<<gp, BLOCK, 0, st>>>((const float*)pts, c, rows_total, (float*)xyz);
+    else                   normals_pack_kernel<double><<<gp, BLOCK, 0, st>>>((const double*)pts, c, rows_total, (double*)xyz);
+    if ((rc = launch_status())) return rc;
+    rc = dicp_sweep_sort(dtype, xyz, 3, nullptr, rows, N, m, m_pad, ws + L.keys, tperm, 0, nullptr, nullptr,
+                         L.scratch_bytes ? ws + L.scratch : nullptr, L.scratch_bytes, stream);
+    if (!rc) rc = dicp_sweep_build(dtype, xyz, 3, nullptr, rows, tperm, N, m, m_pad, ws + L.tgs4, nullptr, 0, stream);
+    if (rc) return rc;
+    const int bpc = (m_pad + BLOCK - 1) / BLOCK;
+    const unsigned g = grid_for(N, bpc);
+    const int vs = vp_per_cloud ? 3 : 0;
+    begin_launch();
+#define DICP_NRM_KNN(T, KK) normals_knn_kernel<T, KK><<<g, BLOCK, 0, st>>>((const V4<T>::type*)(ws + L.tgs4), tperm, rows, N, m, m_pad, k, bpc, nbr_s, neighbors, walked)
+#define DICP_NRM(T) do { \
+        const int kc = nrm_kcap(k); \
+        if (kc == 8) DICP_NRM_KNN(T, 8); else if (kc == 16) DICP_NRM_KNN(T, 16); else DICP_NRM_KNN(T, 32); \
+        normals_point_kernel<T><<<g, BLOCK, 0, st>>>((const V4<T>::type*)(ws + L.tgs4), tperm, rows, N, m, m_pad, k, bpc, nbr_s, (const T*)viewpoint, vs, \
+                                                      (T*)normals, (T*)curvature); } while (0)
+    if (dtype == DICP_F32) DICP_NRM(float); else DICP_NRM(double);
+#undef DICP_NRM
+#undef DICP_NRM_KNN
+    return launch_status();
+}
+
+int dicp_normals_backward(int dtype, const void* g_normals, const void* g_curvature, const void* viewpoint, int vp_per_cloud, const int32_t* rows,
+                          int N, int m, int k, int c, const void* fwd_workspace, void* grad_pts, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!fwd_workspace || !grad_pts || !workspace) return DICP_ERR_NULL;
+    int rc = nrm_check(dtype, N, m, k, vp_per_cloud);
+    if (rc) return rc;
+    if (c < 3 || workspace_bytes < dicp_normals_workspace_bytes(dtype, N, m, k, c, 1)) return DICP_ERR_SHAPE;
+    const size_t ts = dtype == DICP_F32 ? 4 : 8;
+    if ((uintptr_t)fwd_workspace % 256 || (uintptr_t)workspace % 16 || (uintptr_t)grad_pts % ts || (g_normals && (uintptr_t)g_normals % ts) ||
+        (g_curvature && (uintptr_t)g_curvature % ts) || (viewpoint && (uintptr_t)viewpoint % ts)) return DICP_ERR_ALIGN;
+    hipStream_t st = (hipStream_t)stream;
+    const NrmLayout L = nrm_layout(dtype, N, m, k);
+    const char* ws = (const char*)fwd_workspace;
+    const int m_pad = dicp_padded_targets(m);
+    const int32_t* tperm = (const int32_t*)(ws + L.tperm);
+    const size_t gs_bytes = (size_t)N * m_pad * 3 * ts;
+    if ((rc = dicp_fill::zero(workspace, gs_bytes, st))) return rc;
+    if ((rc = dicp_fill::zero(grad_pts, (size_t)N * m * c * ts, st))) return rc;
+    if (!g_normals && !g_curvature) return 0;
+    const int bpc = (m_pad + BLOCK - 1) / BLOCK;
+    const unsigned g = grid_for(N, bpc);
+    const int vs = vp_per_cloud ? 3 : 0;
+    begin_launch();
+#define DICP_NRM_BWD(T) normals_bwd_kernel<T><<<g, BLOCK, 0, st>>>((const V4<T>::type*)(ws + L.tgs4), tperm, rows, N, m, m_pad, k, bpc, \
+        (const int32_t*)(ws + L.nbr_s), (const T*)viewpoint, vs, (const T*)g_normals, (const T*)g_curvature, (T*)workspace)
+    if (dtype == DICP_F32) DICP_NRM_BWD(float); else DICP_NRM_BWD(double);
+#undef DICP_NRM_BWD
+    if ((rc = launch_status())) return rc;
+    return dicp_permute_add_rows(dtype, workspace, tperm, N, m_pad, m_pad, m_pad, 3, 3, grad_pts, m, c, stream);
+}

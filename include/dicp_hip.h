@@ -817,6 +817,27 @@ int dicp_kabsch_call_plan(int dtype, const dicp_kabsch_call* call, dicp_kabsch_c
 int dicp_kabsch_call_forward(int dtype, const dicp_kabsch_call* call, void* stream);
 int dicp_kabsch_call_backward(int dtype, const dicp_kabsch_call* call, const dicp_kabsch_call_grads* grads, void* stream);
 
+/* Surface normals for point-to-plane targets (dicp_amd/normals.py; the reference takes them as given, ICP.py:101-105).
+ *   pts (N,m,c) T, c >= 3, columns 0:3 used; rows: optional (N) row counts as tgt_rows; 3 <= k <= 32.
+ *   For point i of cloud b: its k_eff = min(k, rows[b]) nearest rows of the same cloud in (d2, index) order, d2 = (dx*dx + dy*dy) + dz*dz as three
+ *   separate products (no fused multiply-add), itself included; C = the covariance of their offsets q_j = p_j - p_i about their mean (two passes);
+ *   normal = the eigenvector of C's smallest eigenvalue (svd3, double), oriented so that n . (viewpoint - p_i) >= 0 (on exactly 0: first nonzero
+ *   component positive); curvature = lam0 / (lam0 + lam1 + lam2), 0 for a zero trace.  k_eff < 3 and pad rows: zero normal, zero curvature.
+ *   viewpoint: NULL (the origin), (3) T (vp_per_cloud = 0) or (N,3) T (vp_per_cloud = 1).
+ * dicp_normals_workspace_bytes: the bytes of the workspace of the forward (backward = 0) or of the backward (backward = 1); 0 for bad arguments.
+ * dicp_normals_forward: normals (N,m,3) T and curvature (N,m) T (may be NULL) written; neighbors (N,m,k) int64 (may be NULL): the original row
+ *   indices, -1 beyond k_eff and on pad rows.  The workspace (256-byte aligned) holds the sorted rows and the neighbour slots the backward reads:
+ *   keep it unchanged until then.  walked: optional (N) counters of the rows the search visited (diagnostics; zeroed first).
+ * dicp_normals_backward: grad_pts (N,m,c) T written (columns 3:c zero) from g_normals (N,m,3) and g_curvature (N,m) (either may be NULL), with the
+ *   forward's arguments and its workspace.  A point whose two smallest eigenvalues are not separated (lam1 - lam0 <= tau (lam0 + lam1 + lam2), tau =
+ *   1e-6 float32 / 1e-12 float64) contributes nothing.  Sums through float atomics: not bit-reproducible from run to run. */
+size_t dicp_normals_workspace_bytes(int dtype, int N, int m, int k, int c, int backward);
+int dicp_normals_forward(int dtype, const void* pts, int c, const int32_t* rows, int N, int m, int k, const void* viewpoint, int vp_per_cloud,
+                         void* normals, void* curvature, int64_t* neighbors, void* workspace, size_t workspace_bytes,
+                         unsigned long long* walked, void* stream);
+int dicp_normals_backward(int dtype, const void* g_normals, const void* g_curvature, const void* viewpoint, int vp_per_cloud, const int32_t* rows,
+                          int N, int m, int k, int c, const void* fwd_workspace, void* grad_pts, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
