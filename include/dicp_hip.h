@@ -838,6 +838,29 @@ int dicp_normals_forward(int dtype, const void* pts, int c, const int32_t* rows,
 int dicp_normals_backward(int dtype, const void* g_normals, const void* g_curvature, const void* viewpoint, int vp_per_cloud, const int32_t* rows,
                           int N, int m, int k, int c, const void* fwd_workspace, void* grad_pts, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Voxel-grid downsampling (dicp_amd/voxel.py).
+ *   pts (N,m,c) T, c >= 3; rows: optional (N) row counts as tgt_rows.  Row r of cloud b takes part when r < rows[b] and its x, y, z are finite.
+ *   v_d = floor((p_d - o_d) / s_d) in T (o and s converted to T first; one rounded subtraction, one IEEE division); |v_d| >= 2^62 fails the cloud,
+ *   and so does w_x + w_y + w_z > 64 with w_d = bit_length(max v_d - min v_d) over its rows.  A cloud's voxels are its distinct (vx, vy, vz) with
+ *   at least min_points rows, in ascending lexicographic order; a centroid is the mean of all c columns of its rows, summed in double in row
+ *   order, divided by the count and rounded once to T.  No float atomics: the results are bit-reproducible from run to run.
+ *   s = (sx, sy, sz) > 0 finite; origin: NULL (the origin), (3) T (origin_per_cloud = 0) or (N,3) T (origin_per_cloud = 1).
+ * dicp_voxel_workspace_bytes: the bytes of the workspace both phases share; 0 for bad arguments.
+ * dicp_voxel_count: the count phase.  rows_out (N + 1) int32 written: each cloud's number of voxels, then the error word -- 0, or
+ *   ((first failing cloud + 1) << 2) | code, code 1 = a coordinate out of range, 2 = more than 64 key bits.  The workspace (256-byte aligned)
+ *   holds the sorted rows and the voxels' extents: keep it unchanged until dicp_voxel_reduce.
+ * dicp_voxel_reduce: centroids (N,M,c) T, counts (N,M) int32 and inverse (N,m) int64 written, M >= max rows_out (M = 0: the inverse only):
+ *   rows at or past rows_out[b] zero, inverse = the row's voxel or -1 (a row that does not take part, or whose voxel has < min_points rows).
+ * dicp_voxel_backward: grad_pts (N,m,c) T = grad_centroids[b, inverse] / (T)counts[b, inverse] (one IEEE division per element), 0 where the
+ *   inverse is -1. */
+size_t dicp_voxel_workspace_bytes(int dtype, int N, int m, int c);
+int dicp_voxel_count(int dtype, const void* pts, int c, const int32_t* rows, int N, int m, double sx, double sy, double sz,
+                     const void* origin, int origin_per_cloud, int min_points, int32_t* rows_out, void* workspace, size_t workspace_bytes, void* stream);
+int dicp_voxel_reduce(int dtype, const void* pts, int c, int N, int m, int M, const void* workspace, size_t workspace_bytes,
+                      void* centroids, int32_t* counts, int64_t* inverse, void* stream);
+int dicp_voxel_backward(int dtype, const void* grad_centroids, const int64_t* inverse, const int32_t* counts, int N, int m, int M, int c,
+                        void* grad_pts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

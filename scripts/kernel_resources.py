@@ -21,7 +21,7 @@ names = [r["name"] for r in rows]
 dem = subprocess.run(["c++filt"] + names, capture_output=True, text=True).stdout.splitlines() if names else []
 print("%-6s %-5s %-5s %-8s %-4s %-7s %s" % ("VGPR", "AGPR", "SGPR", "scratch", "occ", "LDS", "kernel"))
 for r, d in zip(rows, dem):
-    d = re.sub(r"^void \(anonymous namespace\)::", "", d)
+    d = re.sub(r"^(void )?\(anonymous namespace\)::", "", d)      # (non-template kernels demangle without their return type)
     d = re.sub(r"\(.*$", "", d)
     if flt.search(d):
         print("%-6d %-5d %-5d %-8d %-4d %-7d %s" % (r.get("vgpr", -1), r.get("agpr", -1), r.get("sgpr", -1), r.get("scratch", -1), r.get("occ", -1), r.get("lds", -1), d))
