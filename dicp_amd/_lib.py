@@ -11,8 +11,8 @@ import threading
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 LIB_PATH = os.environ.get("DICP_HIP_LIB") or os.path.join(_HERE, "libdicp_hip.so")   # env override: A/B builds
-SOURCES = [os.path.join(_HERE, "csrc", f) for f in ("dicp_kernels.hip", "knn_f16.hip", "dicp_call.hip", "normals.hip", "voxel.hip")]
-HEADERS = ([os.path.join(_HERE, "csrc", f) for f in ("dicp_math.h", "dicp_common.h", "dicp_internal.h", "dicp_fill.h", "dicp_normals.h", "dicp_voxel.h")]
+SOURCES = [os.path.join(_HERE, "csrc", f) for f in ("dicp_kernels.hip", "knn_f16.hip", "dicp_call.hip", "normals.hip", "voxel.hip", "knn_points.hip")]
+HEADERS = ([os.path.join(_HERE, "csrc", f) for f in ("dicp_math.h", "dicp_common.h", "dicp_internal.h", "dicp_fill.h", "dicp_normals.h", "dicp_voxel.h", "dicp_topk.h")]
            + [os.path.join(_HERE, "csrc", "kernels_%s.h" % f) for f in ("setup", "search", "setup_sort", "rows", "accumulate", "backward", "soft_svd", "host")]
            + [os.path.join(_ROOT, "include", "dicp_hip.h")])
 
@@ -245,6 +245,9 @@ _SIGNATURES = {
     "dicp_voxel_count": ([i32, vp, i32, vp, i32, i32, f64, f64, f64, vp, i32, i32, vp, vp, ctypes.c_size_t, vp], ctypes.c_int),
     "dicp_voxel_reduce": ([i32, vp, i32, i32, i32, i32, vp, ctypes.c_size_t, vp, vp, vp, vp], ctypes.c_int),
     "dicp_voxel_backward": ([i32, vp, vp, vp, i32, i32, i32, i32, vp, vp], ctypes.c_int),
+    "dicp_knn_points_workspace_bytes": ([i32, i32, i32, i32, i32, i32], ctypes.c_size_t),
+    "dicp_knn_points": ([i32, vp, vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, ctypes.c_size_t, vp, vp], ctypes.c_int),
+    "dicp_knn_points_backward": ([i32, vp, vp, vp, vp, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, ctypes.c_size_t, vp], ctypes.c_int),
 }
 EXPORTS = tuple(_SIGNATURES)
 

@@ -9,7 +9,7 @@
 //            side once gap*gap > the k-th best d2 so far.  Exact: d2 = (xx + yy) + zz >= fl(dx*dx) = fl(gap*gap) for sums of
 //            non-negative terms under round-to-nearest, and every row further out on that side has a larger gap.  Ties at the k-th
 //            d2 are still examined, so the (d2, index) order holds.  The top-k list is a sorted register array, its insertion
-//            unrolled; the block's slots +- WALK_HALO rows are staged in LDS.
+//            unrolled (list and walk: csrc/dicp_topk.h); the block's slots +- WALK_HALO rows are staged in LDS.
 //   normals  one lane per slot: the two-pass covariance of its neighbours, svd3, orientation, curvature (csrc/dicp_normals.h).
 // Backward (dicp_normals_backward): one lane per slot recomputes its eigen-system from the saved neighbour slots and adds
 // (2/k_eff) G (q_j - mu) to each neighbour j: into an LDS window of the block's slots +- BWD_HALO rows with LDS atomics, outside
@@ -21,6 +21,7 @@
 #include "dicp_common.h"
 #include "dicp_fill.h"
 #include "dicp_normals.h"
+#include "dicp_topk.h"
 
 namespace {
 
@@ -66,11 +67,7 @@ __global__ __launch_bounds__(BLOCK) void normals_pack_kernel(const T* __restrict
     o[0] = p[0]; o[1] = p[1]; o[2] = p[2];
 }
 
-// ------------------------------------------------------------------ walk
-// (d2, index) order; the list's unused head is -inf (never beaten), its empty tail +inf with index -1
-template <typename T>
-__device__ __forceinline__ bool nrm_before(T da, int ia, T db, int ib) { return da < db || (da == db && ia < ib); }
-
+// ------------------------------------------------------------------ walk (the list and the two cursors: csrc/dicp_topk.h)
 template <typename T, int K>
 __global__ __launch_bounds__(BLOCK) void normals_knn_kernel(const typename V4<T>::type* __restrict__ tgs4, const int32_t* __restrict__ tperm,
                                                             const int32_t* __restrict__ rows, int N, int m, int m_pad, int k, int bpc,
@@ -92,46 +89,14 @@ __global__ __launch_bounds__(BLOCK) void normals_knn_kernel(const typename V4<T>
     unsigned long long steps = 0;
     if (live) {
         auto row = [&](int j) -> T4 { return (j >= wlo && j < whi) ? win[j - wlo] : tgs4[base + j]; };
+        auto orig = [&](int j) -> int { return tperm[base + j]; };
         T d[K];
         int id[K], sl[K];
-#pragma unroll
-        for (int i = 0; i < K; ++i) { d[i] = i < K - k ? -inf_v<T>() : inf_v<T>(); id[i] = -1; sl[i] = -1; }
+        topk_init(d, id, sl, k);
+        const auto ins = topk_inserter(d, id, sl, orig);
         const T4 p = row(s);
-        auto consider = [&](const T4& y, int j) {
-            const T dx = y.x - p.x;
-            const T dy = y.y - p.y;
-            const T dz = y.z - p.z;
-            const T xx = dx * dx;
-            const T yy = dy * dy;
-            const T zz = dz * dz;
-            const T d2 = (xx + yy) + zz;
-            if (!(d2 <= d[K - 1])) return;
-            const int o = tperm[base + j];
-            if (!nrm_before(d2, o, d[K - 1], id[K - 1])) return;
-#pragma unroll
-            for (int i = K - 1; i > 0; --i) {
-                const bool shift = nrm_before(d2, o, d[i - 1], id[i - 1]);
-                const bool put = !shift && (i == K - 1 || nrm_before(d2, o, d[i], id[i]));
-                d[i] = shift ? d[i - 1] : (put ? d2 : d[i]);
-                id[i] = shift ? id[i - 1] : (put ? o : id[i]);
-                sl[i] = shift ? sl[i - 1] : (put ? j : sl[i]);
-            }
-            if (nrm_before(d2, o, d[0], id[0])) { d[0] = d2; id[0] = o; sl[0] = j; }
-        };
-        consider(p, s);
-        int lo = s - 1, hi = s + 1;
-        bool cl = lo >= 0, ch = hi < mb;
-        T4 yl = row(cl ? lo : s), yh = row(ch ? hi : s);
-        while (cl || ch) {
-            const T gl = p.x - yl.x, gh = yh.x - p.x;
-            const bool left = cl && (!ch || gl <= gh);
-            const T g = left ? gl : gh;
-            const T g2 = g * g;
-            if (g2 > d[K - 1]) break;                       // this side is the nearer one: the other is beyond the bound as well
-            ++steps;
-            if (left) { consider(yl, lo); --lo; cl = lo >= 0; if (cl) yl = row(lo); }
-            else      { consider(yh, hi); ++hi; ch = hi < mb; if (ch) yh = row(hi); }
-        }
+        ins(topk_d2<T>(p, p), s);
+        steps = topk_walk(d, p, s - 1, s + 1, mb, row, ins);
         const size_t q = base + s;
         const int orow = tperm[q];
 #pragma unroll

@@ -861,6 +861,27 @@ int dicp_voxel_reduce(int dtype, const void* pts, int c, int N, int m, int M, co
 int dicp_voxel_backward(int dtype, const void* grad_centroids, const int64_t* inverse, const int32_t* counts, int N, int m, int M, int c,
                         void* grad_pts, void* stream);
 
+/* k nearest neighbours between two clouds and their gradient (dicp_amd/knn.py: knn_points, chamfer_distance).
+ *   Both clouds are prepared first, each once, by dicp_sweep_sort + dicp_sweep_build with frame = NULL and c in {3, 6}: the queries x (N,n,c) give
+ *   x_perm (N,n_pad) and x_tgs4 (N,n_pad,4) T, the targets y (N,m,c) give y_keys (N,m_pad) T, y_perm (N,m_pad) and y_tgs4 (N,m_pad,4) T
+ *   (n_pad / m_pad = dicp_padded_targets); x_rows / y_rows: optional (N) row counts, the same ones the set-up was given.  1 <= k <= 32.
+ *   For query row i < x_rows[b]: the candidates are the rows j < y_rows[b] whose d2 = (xx + yy) + zz (dx = y.x - x.x, xx = dx * dx, ... as separate
+ *   statements: no fused multiply-add) is finite; the result is the first k_eff = min(k, #candidates) of them in (d2, index) order.
+ * dicp_knn_points_workspace_bytes: the bytes of the workspace of the search (backward = 0) or of the backward (backward = 1); 0 for bad arguments.
+ * dicp_knn_points: d2 (N,n,k) T and idx (N,n,k) int64 written in the original query order: +inf / -1 beyond k_eff and on query rows past x_rows[b].
+ *   The workspace (4-byte aligned) holds the sorted target slot of every entry, which the backward reads: keep it unchanged until then.
+ *   walked: optional (N) counters of the rows the search visited (diagnostics; zeroed first).  No float atomics: bit-reproducible.
+ * dicp_knn_points_backward: from g_d2 (N,n,k) T, the prepared clouds and the search's workspace: grad_x (N,n,cx) T = sum_o 2 g_io (x_i - y_idx)
+ *   in list order, written once (bit-reproducible), and grad_y (N,m,cy) T = -sum 2 g_io (x_i - y_l) over the entries with idx = l, through float
+ *   atomics (not bit-reproducible); columns 3: and pad rows zero; either may be NULL (the workspace, 16-byte aligned, is needed for grad_y only). */
+size_t dicp_knn_points_workspace_bytes(int dtype, int N, int n, int m, int k, int backward);
+int dicp_knn_points(int dtype, const void* x_tgs4, const int32_t* x_perm, const int32_t* x_rows, int n,
+                    const void* y_keys, const void* y_tgs4, const int32_t* y_perm, const int32_t* y_rows, int m, int N, int k,
+                    void* d2, int64_t* idx, void* workspace, size_t workspace_bytes, unsigned long long* walked, void* stream);
+int dicp_knn_points_backward(int dtype, const void* g_d2, const void* x_tgs4, const int32_t* x_perm, const int32_t* x_rows, int n, int cx,
+                             const void* y_tgs4, const int32_t* y_perm, int m, int cy, int N, int k, const void* fwd_workspace,
+                             void* grad_x, void* grad_y, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
