@@ -1,6 +1,9 @@
 """knn_points and chamfer_distance on the MI355X against their definition (dicp_amd/knn.py): neighbours index for index and d2 bit for bit
 against a numpy brute force that computes d2 with the same statements, the input forms and ragged rows, gradients against autograd, the
 agreement with estimate_normals' own search, reproducibility, and the Chamfer distance alone and through a differentiable ICP call."""
+import os
+import sys
+
 import numpy as np
 import pytest
 import torch
@@ -9,33 +12,10 @@ from dicp_amd.knn import chamfer_distance, knn_points
 from dicp_amd.normals import estimate_normals
 from dicp_amd.synthetic import make_pairs
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from walk_layouts import chamfer_oracle as _chamfer_oracle, knn_oracle as _oracle  # noqa: E402  (the brute forces, shared with test_gpu_knn_walk.py)
+
 pytestmark = pytest.mark.gpu
-
-
-def _oracle(X, Y, k, chunk=256):
-    """(n,3), (m,3) numpy in their own dtype -> (d2 (n,k), idx (n,k)): the first min(k, #finite) rows in (d2, index) order, +inf / -1 beyond"""
-    n, m = X.shape[0], Y.shape[0]
-    d2o = np.full((n, k), np.inf, dtype=X.dtype)
-    io = np.full((n, k), -1, dtype=np.int64)
-    for a in range(0, n, chunk):
-        Q = X[a:a + chunk]
-        with np.errstate(invalid="ignore", over="ignore"):
-            dx = Y[None, :, 0] - Q[:, None, 0]
-            dy = Y[None, :, 1] - Q[:, None, 1]
-            dz = Y[None, :, 2] - Q[:, None, 2]
-            xx = dx * dx
-            yy = dy * dy
-            zz = dz * dz
-            d2 = (xx + yy) + zz
-        d2 = np.where(np.isfinite(d2), d2, np.inf)
-        ke = min(k, m)
-        kth = np.partition(d2, ke - 1, axis=1)[:, ke - 1] if m else np.full(Q.shape[0], np.inf)
-        for r in range(Q.shape[0]):
-            cand = np.flatnonzero((d2[r] <= kth[r]) & np.isfinite(d2[r]))
-            order = np.lexsort((cand, d2[r, cand]))[:k]
-            io[a + r, :len(order)] = cand[order]
-            d2o[a + r, :len(order)] = d2[r, cand[order]]
-    return d2o, io
 
 
 def _check(d2, idx, X, Y, k):
@@ -200,21 +180,6 @@ def test_forward_and_x_gradient_bit_reproducible():
 
 
 # ---------------------------------------------------------------- Chamfer distance
-
-def _chamfer_oracle(xs, ys):
-    """per-cloud float64 Chamfer distance from explicit differences (no cdist): lists of (n_b,3) float64 tensors requiring grad -> (N,)"""
-    out = []
-    for x, y in zip(xs, ys):
-        if x.shape[0] and y.shape[0]:
-            d = x[:, None, :] - y[None, :, :]
-            D = (d * d).sum(-1)
-            out.append(D.min(1).values.mean() + D.min(0).values.mean())
-        elif x.shape[0] or y.shape[0]:
-            out.append((x.sum() + y.sum()) * 0 + float("inf"))
-        else:
-            out.append((x.sum() + y.sum()) * 0)
-    return torch.stack(out)
-
 
 @pytest.mark.parametrize("reduction", ["mean", "sum", "none"])
 def test_chamfer_against_float64_oracle(reduction):

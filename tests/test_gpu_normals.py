@@ -1,7 +1,10 @@
 """estimate_normals on the MI355X against its definition (dicp_amd/normals.py): neighbours index for index against a numpy brute force that
 computes d2 with the same statements, normals / curvature against float64 numpy on those neighbourhoods, the scene generator's own normals,
 gradients against autograd, and the plumbing (CPU tensors, lists, padded rows)."""
+import functools
 import math
+import os
+import sys
 
 import numpy as np
 import pytest
@@ -9,6 +12,9 @@ import torch
 
 from dicp_amd.normals import estimate_normals
 from dicp_amd.synthetic import make_pairs, make_scene_pairs
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import walk_layouts as wl  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -147,8 +153,9 @@ def test_gradcheck_float64():
     assert torch.autograd.gradcheck(f, (x,), eps=1e-6, atol=1e-6, rtol=1e-4)
 
 
-def _autograd_oracle(P, nbr, vp, gn):
-    """dL/dP of L = sum gn . n through torch.linalg.eigh in float64 on the given neighbourhoods (the sign taken from the forward)"""
+def _autograd_oracle(P, nbr, vp, gn, gc=None):
+    """dL/dP of L = sum gn . n (+ sum gc curvature) through torch.linalg.eigh in float64 on the given neighbourhoods (the sign taken from the
+    forward)"""
     p = torch.tensor(P, dtype=torch.float64, requires_grad=True)
     idx = torch.tensor(nbr)
     q = p[idx] - p[:, None, :]
@@ -157,7 +164,10 @@ def _autograd_oracle(P, nbr, vp, gn):
     w, V = torch.linalg.eigh(C)
     v0 = V[:, :, 0]
     s = torch.where(((torch.tensor(vp)[None] - p.detach()) * v0.detach()).sum(1) < 0, -1.0, 1.0).to(torch.float64)
-    (gn * (s[:, None] * v0)).sum().backward()
+    L = (gn * (s[:, None] * v0)).sum()
+    if gc is not None:
+        L = L + (gc * w[:, 0] / w.sum(1)).sum()
+    L.backward()
     return p.grad.numpy()
 
 
@@ -242,3 +252,160 @@ def test_list_padded_and_separate_agree(dtype):
     for b in range(4):
         assert torch.all(x.grad[b, lens[b]:] == 0)
     assert torch.all(x.grad[..., 3:] == 0)
+
+
+# ---------------------------------------------------------------- neighbour lists that leave the LDS windows (tests/walk_layouts.py)
+#
+# The layouts `wall` (20000 rows, x in +-1e-3) and `cube` (40000 uniform rows) put 83-88 % and 18-47 % of the backward's (query, neighbour)
+# entries outside the block's window (csrc/normals.hip: global atomics instead of LDS atomics); every case asserts that share with the numpy
+# window model on the brute force's lists before it looks at a GPU result.
+
+WALK_DTYPES = [torch.float32, torch.float64]
+WALK_IDS = ["f32", "f64"]
+WALK_VP = np.array([5.0, 0.3, -0.2])                         # in front of the wall: its normals are +x there
+
+
+@functools.lru_cache(maxsize=None)
+def _walk_case(name, dtype):
+    """-> (points in the dtype, k, the brute force's neighbour lists, the window model on them), the layout's condition asserted"""
+    P, k = wl.normals_layout(name)
+    P = P.astype(wl.np_dtype(dtype))
+    ref = _knn_oracle(P, k)
+    w = wl.normals_windows(P, k, dtype, ref)
+    print("normals %s %s: backward entries outside the window %.3f, max in-degree %d" % (name, P.dtype.name, w.share(), w.indegree.max()))
+    wl.check_normals_conditions(name, dtype, w)
+    return P, k, ref, w
+
+
+@pytest.mark.parametrize("dtype", WALK_DTYPES, ids=WALK_IDS)
+def test_walk_neighbours_exact_on_the_wall(dtype):
+    P, k, ref, _ = _walk_case("wall", dtype)
+    nbr = estimate_normals(torch.from_numpy(P).cuda(), k=k, return_neighbors=True)[1].cpu().numpy()
+    assert np.array_equal(nbr, ref), "%d rows differ" % int((nbr != ref).any(1).sum())
+
+
+def _walk_batch(dtype):
+    """N = 3: wall, cube and a ragged cloud, padded to 40000 rows with points that would be neighbours if a row count were ignored"""
+    dt = wl.np_dtype(dtype)
+    Pw, k, ref_w, _ = _walk_case("wall", dtype)
+    Pc, _, ref_c, _ = _walk_case("cube", dtype)
+    rows = [Pw.shape[0], Pc.shape[0], 12345]
+    pts = np.stack([wl.wall(40000, 31), wl.cube(40000, 32), wl.cube(40000, 33)]).astype(dt)
+    pts[0, :rows[0]], pts[1] = Pw, Pc
+    return pts, rows, k, [ref_w, ref_c, None]
+
+
+@pytest.mark.parametrize("dtype", WALK_DTYPES, ids=WALK_IDS)
+def test_walk_neighbours_exact_in_a_ragged_batch(dtype):
+    pts, rows, k, refs = _walk_batch(dtype)
+    nbr = estimate_normals(torch.from_numpy(pts).cuda(), k=k, rows=torch.tensor(rows, dtype=torch.int32).cuda(), return_neighbors=True)[1].cpu().numpy()
+    for b in range(3):
+        ref = refs[b] if refs[b] is not None else _knn_oracle(pts[b, :rows[b]], k)
+        assert np.array_equal(nbr[b, :rows[b]], ref), "cloud %d: %d rows differ" % (b, int((nbr[b, :rows[b]] != ref).any(1).sum()))
+        assert np.all(nbr[b, rows[b]:] == -1)
+
+
+@pytest.mark.parametrize("dtype,tol", [(torch.float64, 1e-10), (torch.float32, 1e-4)], ids=["f64", "f32"])
+def test_walk_normals_match_oracle_on_the_wall(dtype, tol):
+    P, k, ref, _ = _walk_case("wall", dtype)
+    nrm, curv, nbr = estimate_normals(torch.from_numpy(P).cuda(), k=k, viewpoint=torch.tensor(WALK_VP, dtype=dtype), return_curvature=True,
+                                      return_neighbors=True)
+    nrm, curv, nbr = nrm.cpu().numpy().astype(np.float64), curv.cpu().numpy(), nbr.cpu().numpy()
+    assert np.array_equal(nbr, ref)
+    n_ref, c_ref, gap = _normals_oracle(P, nbr, WALK_VP)
+    assert gap.min() > 1e-3                                  # a wall: every normal is well defined
+    ang = np.linalg.norm(np.cross(nrm, n_ref), axis=1) / np.linalg.norm(nrm, axis=1)
+    assert ang.max() <= tol
+    assert np.all(np.einsum("ma,ma->m", nrm, n_ref) > 0)
+    assert np.all(n_ref[:, 0] > 0.9) and np.all(nrm[:, 0] > 0.9)         # +x, towards the viewpoint
+    np.testing.assert_allclose(np.linalg.norm(nrm, axis=1), 1.0, atol=1e-6 if dtype == torch.float32 else 1e-12)
+    np.testing.assert_allclose(curv, c_ref, rtol=1e-4 if dtype == torch.float32 else 1e-9, atol=1e-6 if dtype == torch.float32 else 1e-13)
+
+
+# The bars of the gradient tests below are the existing ones: float32 |got - ref| / |ref| < 1e-3 per cloud (test_gradient_float32_against_float64_oracle),
+# float64 1e-9 (test_gradient_through_pt2pl_icp).  The reference is float64 autograd through torch.linalg.eigh on the kernel's neighbourhoods; the
+# closed form of walk_layouts.normals_grad_closed_form is a second evaluation of it, and the tests print the two references' disagreement.
+# (Float64, on the host: the two references differ by 6e-16 of the gradient's norm on wall and 3e-15 on cube, six orders under the float64 bar.)
+WALK_BAR = {torch.float32: 1e-3, torch.float64: 1e-9}
+GAP_MIN = 1e-2                                               # g is zeroed where (lam1 - lam0) / trace of the reference is below this
+
+
+def _walk_upstream(P, nbr, seed):
+    """random g_nrm (m,3) and g_curv (m,) in float64, zero on the rows whose reference eigen gap is below GAP_MIN (at most 5 % of them)"""
+    rng = np.random.default_rng(seed)
+    m = P.shape[0]
+    gn, gc = rng.standard_normal((m, 3)), rng.standard_normal(m)
+    gap = _normals_oracle(P, nbr, WALK_VP)[2]
+    low = gap < GAP_MIN
+    assert low.mean() <= 0.05, low.mean()
+    gn[low], gc[low] = 0.0, 0.0
+    return gn, gc
+
+
+def _walk_backward(pts, k, gn, gc, dtype, rows=None):
+    """estimate_normals forward + backward on the GPU with both upstream gradients -> (neighbours, points' gradient) as numpy"""
+    x = torch.from_numpy(pts).cuda().requires_grad_(True)
+    nrm, curv, nbr = estimate_normals(x, k=k, viewpoint=torch.tensor(WALK_VP, dtype=dtype), rows=rows, return_curvature=True, return_neighbors=True)
+    torch.autograd.backward([nrm, curv], [torch.from_numpy(gn).to(dtype).cuda(), torch.from_numpy(gc).to(dtype).cuda()])
+    return nbr.cpu().numpy(), x.grad.cpu().numpy()
+
+
+@pytest.mark.parametrize("dtype", WALK_DTYPES, ids=WALK_IDS)
+@pytest.mark.parametrize("name", wl.NORMALS_LAYOUTS)
+def test_walk_gradient_against_float64_oracle(name, dtype):
+    P, k, ref_nbr, w = _walk_case(name, dtype)
+    dt = wl.np_dtype(dtype)
+    gn, gc = _walk_upstream(P, ref_nbr, 41)
+    gn, gc = gn.astype(dt).astype(np.float64), gc.astype(dt).astype(np.float64)      # (what the kernel is given, exactly)
+    nbr, got = _walk_backward(P, k, gn, gc, dtype)
+    assert np.array_equal(nbr, ref_nbr)
+    ref = _autograd_oracle(P.astype(np.float64), nbr, WALK_VP, torch.from_numpy(gn), torch.from_numpy(gc))
+    c, ref2 = wl.normals_grad_closed_form(P, nbr, WALK_VP, gn, gc)
+    err = np.linalg.norm(got - ref) / np.linalg.norm(ref)
+    print("normals %s %s: |got - autograd| / |autograd| = %.3e, |closed form - autograd| / |autograd| = %.3e"
+          % (name, dt.name, err, np.linalg.norm(ref2 - ref) / np.linalg.norm(ref)))
+    assert err < WALK_BAR[dtype], err
+
+    # The eigen part of the backward is per query and the scatter is linear: the gradient for g on the half of the queries with the most
+    # entries outside the window plus the gradient for g on the other half is the gradient for all of g, up to the order of the sums.  Row l
+    # with in-degree D_l: (D_l + 2) u_T sum |contribution| over its entries.  The kernel does not expose its per-entry contributions, and the
+    # two partial gradients only give |sum| <= sum |.|, so sum |contribution| is taken from the closed form on the same neighbourhoods (float64,
+    # within 1e-14 of the kernel's terms).  Each term is rounded to T identically in all three runs, so only the additions differ: the strict
+    # worst case over three sums in unspecified orders is (D - 1) + (D_a - 1) + (D_b - 1) = (2 D - 3) u_T sum |contribution|, above D + 2 for
+    # D > 5.  The bar stays at the D + 2 this check was specified with: rounding errors of the additions do not align, a row's error grows like
+    # sqrt(D) u_T, and the worst ratio printed below is the margin actually seen.
+    out = w.bwd_outside.sum(1)
+    order = np.argsort(-out, kind="stable")
+    half = np.zeros(P.shape[0], bool)
+    half[order[:P.shape[0] // 2]] = True
+    assert out[half].sum() >= 0.5 * out.sum() and out[half].sum() > 0
+    parts = []
+    for sel in (half, ~half):
+        parts.append(_walk_backward(P, k, np.where(sel[:, None], gn, 0.0), np.where(sel, gc, 0.0), dtype)[1].astype(np.float64))
+    A = np.zeros((P.shape[0], 3))
+    for a in range(3):
+        A[:, a] = np.bincount(nbr.reshape(-1), weights=np.abs(c[:, :, a]).reshape(-1), minlength=P.shape[0])
+    bound = ((w.indegree + 2) * wl.U[dt])[:, None] * A
+    r = wl.assert_within(got, parts[0] + parts[1], bound, "normals %s: halves against the whole" % name)
+    print("normals %s %s: halves against the whole, worst error / bound %.3f" % (name, dt.name, r))
+
+
+@pytest.mark.parametrize("dtype", WALK_DTYPES, ids=WALK_IDS)
+def test_walk_gradient_in_a_ragged_batch_against_single_calls(dtype):
+    pts, rows, k, _ = _walk_batch(dtype)
+    dt = wl.np_dtype(dtype)
+    ups = []
+    for b in range(3):
+        nb = estimate_normals(torch.from_numpy(pts[b, :rows[b]]).cuda(), k=k, return_neighbors=True)[1].cpu().numpy()
+        gn, gc = _walk_upstream(pts[b, :rows[b]], nb, 50 + b)
+        ups.append((gn.astype(dt).astype(np.float64), gc.astype(dt).astype(np.float64)))
+    gn, gc = np.random.default_rng(60).standard_normal((3, 40000, 3)), np.random.default_rng(61).standard_normal((3, 40000))   # (pad rows: ignored)
+    for b in range(3):
+        gn[b, :rows[b]], gc[b, :rows[b]] = ups[b]
+    _, got = _walk_backward(pts, k, gn, gc, dtype, rows=torch.tensor(rows))
+    for b in range(3):
+        _, one = _walk_backward(pts[b, :rows[b]], k, ups[b][0], ups[b][1], dtype)
+        err = np.linalg.norm(got[b, :rows[b]].astype(np.float64) - one) / np.linalg.norm(one)
+        print("normals batch cloud %d %s: |batch - single| / |single| = %.3e" % (b, dt.name, err))
+        assert err < WALK_BAR[dtype], err
+        assert np.all(got[b, rows[b]:] == 0)
