@@ -66,6 +66,14 @@ DICP_HD int tri(int i, int j) { return i * 6 - (i * (i - 1)) / 2 + (j - i); }   
 // and 0 for |b| > 2^126 -- and a * rcp(a) is not exactly 1: a Huber / Cauchy weight at a residual of exactly the metric comes out 0.99999994.  The quotients here
 // are metric / residual, 1 / (1 + (e/c)^2) and trim / loss ratios of coordinates in metres: neither range occurs; 0 / 0 and x / 0 stay NaN / inf as in the
 // reference (the hard Huber slope's NaN at a zero residual is kept: tests/test_gpu_parity.py).
+// Edges of the range (float32; no LiDAR cloud produces them: residuals of 1e-20 m or 1e20 m; held as they are by tests/test_gpu_point_math.py and
+// tests/test_point_math_ref.py, so that they cannot change unnoticed):
+//   a residual whose square underflows (|e3| <= 1e-23; on the device from |e3| <= 1e-19 on, because v_sqrt_f32 reads a denormal d3^2 as 0): d3 = 0, and
+//     point_backward's `s.d3 > T(0)` drops the gradient terms that pass |e3| -- the soft trim gate's 0.5 k (1 - th^2) e3/|e3| and the loss slope's -- exactly as it
+//     does at a zero residual; pt2pt with the hard Huber weight then also takes the zero-residual branch of hard_huber_slope: gsrc, gtgt and the pose sums are NaN.
+//   a residual whose square overflows (|e3| >= 1.9e19): d3 = inf; pt2pt with the differentiable Huber or the Cauchy weight has lw = 0 and the slope
+//     -2 en lw^2 / metric^2 = inf * 0 = NaN: gsrc, gtgt and the pose sums are NaN (w, the slots, gw stay finite: w = 0).  loss_weight_bwd_kernel does the same.
+//   Everything else at those residuals equals the float64 evaluation, or the float64 evaluation with d3 = 0, within first order.
 #if defined(__HIP_DEVICE_COMPILE__)
 DICP_HD float  m_sqrt(float x)  { return __builtin_amdgcn_sqrtf(x); }
 DICP_HD float  m_div(float a, float b) { return a * __builtin_amdgcn_rcpf(b); }

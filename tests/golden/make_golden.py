@@ -337,6 +337,32 @@ def loss_vectors():
     save("loss_vectors", **arrs)
 
 
+def loss_vectors_f32():
+    """The stand-alone loss at its edges, in float32 and in float64 on the SAME float32-rounded inputs: zero residual, residual exactly the metric,
+    tiny and huge residuals (en^2 subnormal, underflowing, overflowing in float32) and a few ordinary ones.  tests/test_point_math_ref.py pins the
+    float64 reference of tests/point_math_ref.py to the float64 outputs and holds the float32 outputs to its error model.  (1, n, r) inputs: the
+    3-D form, one weight per row for every loss.  Metrics exactly representable, so that both dtypes see the same one."""
+    arrs = {}
+    for name, metric in (("huber", 1.0), ("cauchy", 0.5), ("trim", 2.0)):
+        vals = np.array([0.0, 0.0, metric, -metric, 1e-20, 1e-30, 1e20, -1e-20, -1e-30, -1e20, 0.25, -1.75, 3.0], dtype=np.float32)
+        e1 = vals.reshape(1, -1, 1)
+        e3 = np.zeros((1, len(vals), 3), dtype=np.float32)
+        e3[0, :, 2] = vals
+        e3[0, -3:, 0] = np.array([0.5, -0.25, 1.0], dtype=np.float32)
+        arrs[name + "_e1"], arrs[name + "_e3"] = e1, e3
+        for diff in (True, False):
+            for tag, e in (("e1", e1), ("e3", e3)):
+                for dt, dtag in ((torch.float32, "f32"), (torch.float64, "f64")):
+                    et = torch.tensor(e, dtype=dt, requires_grad=True)
+                    w = RefLoss(name=name, metric=metric, differentiable=diff, tanh_steepness=5.0).get_weight(et)
+                    key = "%s_%s_%s_%s" % (name, "diff" if diff else "hard", tag, dtag)
+                    arrs[key] = npy(w)
+                    if w.requires_grad:
+                        w.sum().backward()
+                        arrs[key + "_grad"] = npy(et.grad)
+    save("loss_vectors_f32", **arrs)
+
+
 def svd_planar():
     """ICP.pt2pt_dICP_SVD (ICP.py:533-591) on the bundled planar pair -- the one setting where the
     reference's V-for-V^T composition is harmless."""
@@ -379,5 +405,6 @@ if __name__ == "__main__":
     matrix3d_trimloss()
     nn_vectors()
     loss_vectors()
+    loss_vectors_f32()
     svd_planar()
     svd_tinit()

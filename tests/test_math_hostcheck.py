@@ -9,7 +9,7 @@ SURVEY.md section 8(a-11) without a GPU.
 import ctypes
 import os
 import shutil
-import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -19,26 +19,15 @@ import torch
 from oracle import dicp_oracle as O
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "hostcheck", "hostcheck.cpp")
-LIB = os.path.join(HERE, "hostcheck", "libhostcheck.so")
+sys.path.insert(0, HERE)
+from point_math_ref import WeightParams, load_hostcheck  # noqa: E402  (the loader of the g++ build, shared with tests/test_point_math_ref.py)
 
 pytestmark = pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
 
 
-class WeightParams(ctypes.Structure):
-    _fields_ = [("mode", ctypes.c_int), ("trim_on", ctypes.c_int), ("differentiable", ctypes.c_int),
-                ("loss", ctypes.c_int), ("trim_dist", ctypes.c_double), ("tanh_k", ctypes.c_double),
-                ("loss_delta", ctypes.c_double), ("match_thresh", ctypes.c_double)]
-
-
 @pytest.fixture(scope="module")
 def hc():
-    hdr = os.path.join(HERE, "..", "dicp_amd", "csrc", "dicp_math.h")
-    if (not os.path.exists(LIB) or os.path.getmtime(LIB) < max(os.path.getmtime(SRC), os.path.getmtime(hdr))):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-Wno-unknown-pragmas", "-o", LIB, SRC])
-    lib = ctypes.CDLL(LIB)
-    assert lib.hc_sizeof_params() == ctypes.sizeof(WeightParams)
-    return lib
+    return load_hostcheck()
 
 
 def ptr(a):
