@@ -882,6 +882,27 @@ int dicp_knn_points_backward(int dtype, const void* g_d2, const void* x_tgs4, co
                              const void* y_tgs4, const int32_t* y_perm, int m, int cy, int N, int k, const void* fwd_workspace,
                              void* grad_x, void* grad_y, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Farthest-point sampling (dicp_amd/fps.py: sample_farthest_points).
+ *   pts (N,n,c) T, c >= 3; rows: optional (N) row counts as tgt_rows; start: optional (N) int64 >= 0, the row pick 0 starts from (NULL: row 0).
+ *   d2(a, b) = (xx + yy) + zz with dx = b.x - a.x, xx = dx * dx, ... as separate roundings in T.  The candidates of cloud b are the rows
+ *   j < rows[b] with finite x, y, z; k_eff = min(k, #candidates).  Pick 0 is the candidate with the smallest (j - start[b]) mod rows[b];
+ *   pick t >= 1 the candidate not picked yet with the largest D_j = min over the earlier picks s of d2(p_j, p_s), the lowest index among
+ *   equals (+inf from an overflow is an ordinary value).  No float atomics anywhere: bit-reproducible.
+ *   form: DICP_FPS_AUTO takes the resident form (one workgroup per cloud, the cloud in registers) for n <= resident_rows and the streamed
+ *   form (one launch per pick, the state in the workspace) beyond; the other two force one (tests); the resident form refuses a larger n.
+ * dicp_fps_geometry: the resident workgroup's threads, the largest n of the resident form for the dtype, the rows per workgroup of the
+ *   streamed form (each pointer optional).
+ * dicp_fps_workspace_bytes: the bytes dicp_fps_forward needs for (n, form): 0 for the resident form, and for bad arguments.
+ * dicp_fps_forward: out (N,k,c) T = the picked rows, idx (N,k) int64, dist (N,k) T = the D of each pick when it was made (+inf for pick 0),
+ *   k_eff (N) int32; slots at or past k_eff[b]: zero rows, idx -1, dist +inf.  The workspace (256-byte aligned) is scratch.
+ * dicp_fps_backward: grad_pts (N,n,c) T = zero (a fill kernel), then grad_pts[b, idx[b, s]] = grad_out[b, s] for idx >= 0 (distinct per cloud). */
+enum { DICP_FPS_AUTO = 0, DICP_FPS_RESIDENT = 1, DICP_FPS_STREAMED = 2 };
+void dicp_fps_geometry(int dtype, int* threads, int* resident_rows, int* stream_rows);
+size_t dicp_fps_workspace_bytes(int dtype, int N, int n, int k, int form);
+int dicp_fps_forward(int dtype, const void* pts, int c, const int32_t* rows, const int64_t* start, int N, int n, int k, int form,
+                     void* out, int64_t* idx, void* dist, int32_t* k_eff, void* workspace, size_t workspace_bytes, void* stream);
+int dicp_fps_backward(int dtype, const void* grad_out, const int64_t* idx, int N, int n, int k, int c, void* grad_pts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
