@@ -1,0 +1,369 @@
+// Fixed-radius neighbours on a sorted cell grid (dicp_amd/ball.py: ball_query).  The arithmetic, the exactness proof and the per-query
+// scan are csrc/dicp_ball.h; this file is the device structure around them.
+//
+// The grid of a cloud (dicp_ball_grid_build, order_by = NULL), O(m) memory whatever extent / radius is -- no table of cells:
+//   plan    ball_plan_kernel, one workgroup per cloud: the bounds and the number of the live rows (j < rows[b], three finite coordinates),
+//           then one lane runs ball_plan: origin, search half-width R, cell edges (enlarged until the key fits), key widths.  The host never
+//           learns any of them; the radius itself is read from device memory.
+//   keys    ball_keys_kernel: the 64-bit cell key of every live row, BALL_NO_KEY for the others and for the padding to P = 2^ceil(log2 m).
+//   sort    a bitonic sort of (key, row index) pairs, P per cloud: ball_sort_local sorts chunks of up to 2048 pairs in LDS (every stage
+//           with a stride inside the chunk), ball_sort_global does one stage with a larger stride.  1 + sum_{P' = 4096 .. P} (log2(P' / 2048)
+//           + 1) launches: 10 for 16384 rows.  The pairs are distinct, so the result does not depend on the network: live rows by (key,
+//           index), then the others by index.
+//   pack    ball_pack_kernel: the live rows as (x, y, z, 0) in sorted order.
+// The queries are ordered by the same kernels (order_by = the grid's plans): their key is that of the nearest grid cell, so that the lanes
+// of a wave visit the same cells; the first n sorted slots are exactly the n query rows, the ones without neighbours (past x_rows[b], or
+// with a non-finite coordinate) last.
+// Search (dicp_ball_query), one lane per sorted query slot: ball_scan of dicp_ball.h with the keys, rows and permutation read from global
+// memory (a cloud of 16384 rows is 128 KiB of keys and 256 KiB of rows: L2, and the lanes of a wave read the same lines), the list code
+// and the capacities K of knn_points.  Outputs in the original query order: d2, idx, counts, and the sorted slot of every entry in the
+// workspace for the backward.  Every loop is bounded by the cloud's row count (dicp_ball.h).  No float atomics: bit-reproducible.
+// Backward (dicp_ball_query_backward), one lane per query: the 2 g (x - y) terms in double, the x-gradient summed in list order and written
+// once, the y-gradient added to the original rows with float atomics after a zero-fill kernel (not bit-reproducible from run to run).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "dicp_common.h"
+#include "dicp_fill.h"
+#include "dicp_ball.h"
+
+namespace {
+
+constexpr int BALL_KMAX = 32;
+constexpr int BALL_CHUNK = 2048;                        // pairs a workgroup sorts in LDS: 24 KiB
+
+inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
+inline int ball_slots(int m) { int p = 2; while (p < m) p <<= 1; return p; }
+
+template <typename T>
+__device__ __forceinline__ const BallPlan<T>& plan_of(const void* plans, int b) {
+    return *(const BallPlan<T>*)((const char*)plans + (size_t)b * BALL_PLAN_BYTES);
+}
+
+template <typename T>
+__global__ __launch_bounds__(BLOCK) void ball_plan_kernel(const T* __restrict__ pts, int c, const int32_t* __restrict__ rows, int m,
+                                                          const T* __restrict__ radius, void* __restrict__ plans) {
+    __shared__ T smn[3][BLOCK / WAVE], smx[3][BLOCK / WAVE];
+    __shared__ int scnt[BLOCK / WAVE];
+    const int b = blockIdx.x;
+    const int mb = rows_of(rows, b, m);
+    const T* base = pts + (size_t)b * m * c;
+    T mn[3] = {inf_v<T>(), inf_v<T>(), inf_v<T>()}, mx[3] = {-inf_v<T>(), -inf_v<T>(), -inf_v<T>()};
+    int cnt = 0;
+    for (int j = threadIdx.x; j < mb; j += BLOCK) {
+        const T* p = base + (size_t)j * c;
+        const T x = p[0], y = p[1], z = p[2];
+        if (ball_finite(x) && ball_finite(y) && ball_finite(z)) {
+            ++cnt;
+            mn[0] = min_t(mn[0], x); mn[1] = min_t(mn[1], y); mn[2] = min_t(mn[2], z);
+            mx[0] = max_t(mx[0], x); mx[1] = max_t(mx[1], y); mx[2] = max_t(mx[2], z);
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        cnt += __shfl_xor(cnt, off);
+#pragma unroll
+        for (int d = 0; d < 3; ++d) { mn[d] = min_t(mn[d], __shfl_xor(mn[d], off)); mx[d] = max_t(mx[d], __shfl_xor(mx[d], off)); }
+    }
+    const int w = threadIdx.x / WAVE;
+    if ((threadIdx.x & (WAVE - 1)) == 0) {
+        scnt[w] = cnt;
+        for (int d = 0; d < 3; ++d) { smn[d][w] = mn[d]; smx[d][w] = mx[d]; }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int i = 1; i < BLOCK / WAVE; ++i) {
+            cnt += scnt[i];
+            for (int d = 0; d < 3; ++d) { mn[d] = min_t(mn[d], smn[d][i]); mx[d] = max_t(mx[d], smx[d][i]); }
+        }
+        *(BallPlan<T>*)((char*)plans + (size_t)b * BALL_PLAN_BYTES) = ball_plan<T>(mn, mx, cnt, radius[0]);
+    }
+}
+
+// key / idx (N,P): the pairs to sort.  own = 1: the rows of the grid's own cloud; 0: the queries of another cloud
+template <typename T>
+__global__ __launch_bounds__(BLOCK) void ball_keys_kernel(const T* __restrict__ pts, int c, const int32_t* __restrict__ rows, int N, int m, int P,
+                                                          const void* __restrict__ plans, int own, uint64_t* __restrict__ key, int32_t* __restrict__ idx) {
+    const size_t total = (size_t)N * P;
+    for (size_t e = (size_t)blockIdx.x * BLOCK + threadIdx.x; e < total; e += (size_t)gridDim.x * BLOCK) {
+        const int b = (int)(e / P), j = (int)(e - (size_t)b * P);
+        uint64_t k = BALL_NO_KEY;
+        if (j < rows_of(rows, b, m)) {
+            const BallPlan<T>& pl = plan_of<T>(plans, b);
+            const T* p = pts + ((size_t)b * m + j) * c;
+            const T x = p[0], y = p[1], z = p[2];
+            if (ball_finite(x) && ball_finite(y) && ball_finite(z) && (!own || pl.cnt > 0)) k = ball_point_key(pl, x, y, z);
+        }
+        key[e] = k;
+        idx[e] = j;
+    }
+}
+
+__device__ __forceinline__ bool pair_after(uint64_t ka, int ia, uint64_t kb, int ib) { return ka > kb || (ka == kb && ia > ib); }
+
+// Stages of the bitonic network on LDS-resident chunks of `chunk` pairs (a power of two <= BALL_CHUNK dividing P).
+// k_from = 2: the whole network up to runs of `chunk` (k = 2 .. chunk); otherwise the strides chunk / 2 .. 1 of stage k = k_from.
+__global__ __launch_bounds__(BLOCK) void ball_sort_local(uint64_t* __restrict__ key, int32_t* __restrict__ idx, int P, int chunk, int k_from, size_t chunks) {
+    __shared__ uint64_t sk[BALL_CHUNK];
+    __shared__ int32_t si[BALL_CHUNK];
+    const size_t ch = blockIdx.x;
+    if (ch >= chunks) return;
+    const size_t base = ch * (size_t)chunk;
+    const int i0 = (int)(base % (size_t)P);                 // the chunk's first position inside its cloud
+    for (int t = threadIdx.x; t < chunk; t += BLOCK) { sk[t] = key[base + t]; si[t] = idx[base + t]; }
+    __syncthreads();
+    const int k_to = k_from == 2 ? chunk : k_from;
+    for (int k = k_from; k <= k_to; k <<= 1) {
+        for (int j = min(k, chunk) >> 1; j > 0; j >>= 1) {
+            for (int t = threadIdx.x; t < chunk / 2; t += BLOCK) {
+                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
+                const bool asc = ((i0 + i) & k) == 0;
+                const uint64_t ka = sk[i], kb = sk[l];
+                const int ia = si[i], ib = si[l];
+                if (pair_after(ka, ia, kb, ib) == asc) { sk[i] = kb; sk[l] = ka; si[i] = ib; si[l] = ia; }
+            }
+            __syncthreads();
+        }
+    }
+    for (int t = threadIdx.x; t < chunk; t += BLOCK) { key[base + t] = sk[t]; idx[base + t] = si[t]; }
+}
+
+// One stage (k, j) with j >= the chunk: N * P / 2 compare-exchanges in global memory
+__global__ __launch_bounds__(BLOCK) void ball_sort_global(uint64_t* __restrict__ key, int32_t* __restrict__ idx, int P, int k, int j, size_t pairs) {
+    const int half = P >> 1;
+    for (size_t e = (size_t)blockIdx.x * BLOCK + threadIdx.x; e < pairs; e += (size_t)gridDim.x * BLOCK) {
+        const size_t b = e / half;
+        const int t = (int)(e - b * half);
+        const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
+        const bool asc = (i & k) == 0;
+        uint64_t* kk = key + b * P;
+        int32_t* ii = idx + b * P;
+        const uint64_t ka = kk[i], kb = kk[l];
+        const int ia = ii[i], ib = ii[l];
+        if (pair_after(ka, ia, kb, ib) == asc) { kk[i] = kb; kk[l] = ka; ii[i] = ib; ii[l] = ia; }
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(BLOCK) void ball_pack_kernel(const T* __restrict__ pts, int c, int N, int m, int P, const void* __restrict__ plans,
+                                                          const int32_t* __restrict__ perm, typename V4<T>::type* __restrict__ rows4) {
+    using T4 = typename V4<T>::type;
+    const size_t total = (size_t)N * P;
+    for (size_t e = (size_t)blockIdx.x * BLOCK + threadIdx.x; e < total; e += (size_t)gridDim.x * BLOCK) {
+        const int b = (int)(e / P), s = (int)(e - (size_t)b * P);
+        T4 v = {};
+        if (s < plan_of<T>(plans, b).cnt) {
+            const int j = perm[e];
+            if (j >= 0 && j < m) {
+                const T* p = pts + ((size_t)b * m + j) * c;
+                v.x = p[0]; v.y = p[1]; v.z = p[2];
+            }
+        }
+        rows4[e] = v;
+    }
+}
+
+template <typename T, int K>
+__global__ __launch_bounds__(BLOCK) void ball_query_kernel(const T* __restrict__ x, int cx, int n, int Pn, const uint64_t* __restrict__ xkeys,
+                                                           const int32_t* __restrict__ xperm, const void* __restrict__ plans,
+                                                           const uint64_t* __restrict__ ykeys, const int32_t* __restrict__ yperm,
+                                                           const typename V4<T>::type* __restrict__ yrows4, int m, int Pm, int N, int k, int bpc,
+                                                           T* __restrict__ d2_out, int64_t* __restrict__ idx_out, int32_t* __restrict__ counts,
+                                                           int32_t* __restrict__ slots, unsigned long long* __restrict__ visited) {
+    using T4 = typename V4<T>::type;
+    int b, blk;
+    if (!decode_block(bpc, N, b, blk)) return;
+    const int s = blk * BLOCK + threadIdx.x;
+    unsigned long long steps = 0;
+    if (s < n) {                                            // the first n sorted slots are the n query rows
+        const size_t xs = (size_t)b * Pn + s;
+        const int q = min(max(xperm[xs], 0), n - 1);
+        const bool live = xkeys[xs] != BALL_NO_KEY;
+        const size_t ybase = (size_t)b * Pm;
+        T d[K];
+        int id[K], sl[K];
+        topk_init(d, id, sl, k);
+        int count = 0;
+        if (live) {
+            const BallPlan<T> pl = plan_of<T>(plans, b);
+            const T* xp = x + ((size_t)b * n + q) * cx;
+            T4 p = {};
+            p.x = xp[0]; p.y = xp[1]; p.z = xp[2];
+            const uint64_t* kb = ykeys + ybase;
+            auto keys = [&](int j) -> uint64_t { return kb[j]; };
+            auto row = [&](int j) -> T4 { return yrows4[ybase + j]; };
+            auto orig = [&](int j) -> int { return yperm[ybase + j]; };
+            const auto ins = topk_inserter(d, id, sl, orig);
+            const BallScan r = ball_scan<T>(pl, p, keys, row, ins);
+            count = r.count;
+            steps = r.visited;
+        }
+        const size_t o0 = ((size_t)b * n + q) * k;
+        counts[(size_t)b * n + q] = count;
+#pragma unroll
+        for (int i = 0; i < K; ++i) {
+            if (i < K - k) continue;
+            const int o = i - (K - k);
+            d2_out[o0 + o] = d[i];
+            idx_out[o0 + o] = id[i];
+            slots[o0 + o] = sl[i];
+        }
+    }
+    if (visited) {                                          // diagnostics: rows visited, one atomic per wave
+        unsigned long long t = steps;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) t += __shfl_xor(t, off);
+        if ((threadIdx.x & (WAVE - 1)) == 0 && t) atomicAdd(visited + b, t);
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(BLOCK) void ball_bwd_kernel(const T* __restrict__ g_d2, const T* __restrict__ x, int cx, int n,
+                                                         const typename V4<T>::type* __restrict__ yrows4, const int32_t* __restrict__ yperm,
+                                                         int m, int Pm, int cy, int N, int k, int bpc, const int32_t* __restrict__ slots,
+                                                         T* __restrict__ grad_x, T* __restrict__ grad_y) {
+    int b, blk;
+    if (!decode_block(bpc, N, b, blk)) return;
+    const int i = blk * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const size_t row = (size_t)b * n + i, ybase = (size_t)b * Pm;
+    const T* xp = x + row * cx;
+    const T* g = g_d2 + row * k;
+    const int32_t* sl = slots + row * k;
+    double gx[3] = {0.0, 0.0, 0.0};
+    for (int o = 0; o < k; ++o) {
+        const int j = sl[o];
+        if (j < 0 || j >= Pm) continue;
+        const double f = 2.0 * (double)g[o];
+        if (f == 0.0) continue;
+        const auto y = yrows4[ybase + j];
+        const double e[3] = {(double)xp[0] - (double)y.x, (double)xp[1] - (double)y.y, (double)xp[2] - (double)y.z};
+        gx[0] += f * e[0]; gx[1] += f * e[1]; gx[2] += f * e[2];
+        if (grad_y) {
+            const int l = yperm[ybase + j];
+            if (l >= 0 && l < m) {
+                T* a = grad_y + ((size_t)b * m + l) * cy;
+                unsafeAtomicAdd(a, (T)(-f * e[0])); unsafeAtomicAdd(a + 1, (T)(-f * e[1])); unsafeAtomicAdd(a + 2, (T)(-f * e[2]));
+            }
+        }
+    }
+    if (grad_x) {
+        T* r = grad_x + row * cx;
+        r[0] = (T)gx[0]; r[1] = (T)gx[1]; r[2] = (T)gx[2];
+        for (int a = 3; a < cx; ++a) r[a] = T(0);
+    }
+}
+
+inline int ball_kcap(int k) { return k == 1 ? 1 : (k <= 4 ? 4 : (k <= 8 ? 8 : (k <= 16 ? 16 : 32))); }
+
+int ball_check(int dtype, int N, int m) {
+    if (bad_dtype(dtype)) return DICP_ERR_DTYPE;
+    if (N <= 0 || m <= 0 || m > (1 << 30)) return DICP_ERR_SHAPE;
+    if ((size_t)N * ball_slots(m) > ((size_t)1 << 40)) return DICP_ERR_SHAPE;
+    return 0;
+}
+
+inline unsigned grid_items(size_t n) {
+    const size_t g = (n + BLOCK - 1) / BLOCK;
+    return (unsigned)(g < 1 ? 1 : (g > 65536 ? 65536 : g));
+}
+
+int ball_sort(uint64_t* key, int32_t* idx, int N, int P, hipStream_t st) {
+    const int chunk = P < BALL_CHUNK ? P : BALL_CHUNK;
+    const size_t chunks = (size_t)N * (P / chunk), pairs = (size_t)N * (P / 2);
+    if (chunks > 0x7fffffffu) return DICP_ERR_SHAPE;
+    ball_sort_local<<<(unsigned)chunks, BLOCK, 0, st>>>(key, idx, P, chunk, 2, chunks);
+    for (int k = chunk << 1; k <= P && k > 0; k <<= 1) {
+        for (int j = k >> 1; j >= chunk; j >>= 1) ball_sort_global<<<grid_items(pairs), BLOCK, 0, st>>>(key, idx, P, k, j, pairs);
+        ball_sort_local<<<(unsigned)chunks, BLOCK, 0, st>>>(key, idx, P, chunk, k, chunks);
+    }
+    return 0;
+}
+
+}  // namespace
+
+int dicp_ball_grid_slots(int m) { return m > 0 && m <= (1 << 30) ? ball_slots(m) : 0; }
+int dicp_ball_plan_bytes(void) { return BALL_PLAN_BYTES; }
+
+int dicp_ball_grid_build(int dtype, const void* pts, int c, const int32_t* rows, int N, int m, const void* radius, const void* order_by,
+                         void* plans, uint64_t* keys, int32_t* perm, void* rows4, void* stream) {
+    if (!pts || !keys || !perm) return DICP_ERR_NULL;
+    if (order_by ? (plans || rows4) : (!plans || !rows4 || !radius)) return DICP_ERR_NULL;
+    int rc = ball_check(dtype, N, m);
+    if (rc) return rc;
+    if (c < 3) return DICP_ERR_SHAPE;
+    const size_t ts = dtype == DICP_F32 ? 4 : 8;
+    if ((uintptr_t)pts % ts || (rows && (uintptr_t)rows % 4) || (radius && (uintptr_t)radius % ts) || (order_by && (uintptr_t)order_by % 8) ||
+        (plans && (uintptr_t)plans % 8) || (uintptr_t)keys % 8 || (uintptr_t)perm % 4 || (rows4 && (uintptr_t)rows4 % (4 * ts))) return DICP_ERR_ALIGN;
+    hipStream_t st = (hipStream_t)stream;
+    const int P = ball_slots(m);
+    const size_t total = (size_t)N * P;
+    const void* pl = order_by ? order_by : plans;
+    begin_launch();
+#define DICP_BALL_BUILD(T) do { \
+        if (!order_by) ball_plan_kernel<T><<<N, BLOCK, 0, st>>>((const T*)pts, c, rows, m, (const T*)radius, plans); \
+        ball_keys_kernel<T><<<grid_items(total), BLOCK, 0, st>>>((const T*)pts, c, rows, N, m, P, pl, order_by ? 0 : 1, keys, perm); \
+        if ((rc = ball_sort(keys, perm, N, P, st))) return rc; \
+        if (!order_by) ball_pack_kernel<T><<<grid_items(total), BLOCK, 0, st>>>((const T*)pts, c, N, m, P, plans, perm, (V4<T>::type*)rows4); \
+    } while (0)
+    if (dtype == DICP_F32) DICP_BALL_BUILD(float); else DICP_BALL_BUILD(double);
+#undef DICP_BALL_BUILD
+    return launch_status();
+}
+
+size_t dicp_ball_query_workspace_bytes(int dtype, int N, int n, int k) {
+    if (ball_check(dtype, N, n) || k < 1 || k > BALL_KMAX) return 0;
+    return up256((size_t)N * n * k * 4);
+}
+
+int dicp_ball_query(int dtype, const void* x, int cx, int n, const uint64_t* x_keys, const int32_t* x_perm, const void* y_plans,
+                    const uint64_t* y_keys, const int32_t* y_perm, const void* y_rows4, int m, int N, int k,
+                    void* d2, int64_t* idx, int32_t* counts, void* workspace, size_t workspace_bytes, unsigned long long* visited, void* stream) {
+    if (!x || !x_keys || !x_perm || !y_plans || !y_keys || !y_perm || !y_rows4 || !d2 || !idx || !counts || !workspace) return DICP_ERR_NULL;
+    int rc = ball_check(dtype, N, n);
+    if (rc || (rc = ball_check(dtype, N, m))) return rc;
+    if (cx < 3 || k < 1 || k > BALL_KMAX || workspace_bytes < dicp_ball_query_workspace_bytes(dtype, N, n, k)) return DICP_ERR_SHAPE;
+    const size_t ts = dtype == DICP_F32 ? 4 : 8;
+    if ((uintptr_t)x % ts || (uintptr_t)x_keys % 8 || (uintptr_t)x_perm % 4 || (uintptr_t)y_plans % 8 || (uintptr_t)y_keys % 8 || (uintptr_t)y_perm % 4 ||
+        (uintptr_t)y_rows4 % (4 * ts) || (uintptr_t)d2 % ts || (uintptr_t)idx % 8 || (uintptr_t)counts % 4 || (uintptr_t)workspace % 4 ||
+        (visited && (uintptr_t)visited % 8)) return DICP_ERR_ALIGN;
+    hipStream_t st = (hipStream_t)stream;
+    if (visited && (rc = dicp_fill::zero(visited, (size_t)N * sizeof(unsigned long long), st))) return rc;
+    const int Pn = ball_slots(n), Pm = ball_slots(m);
+    const int bpc = (n + BLOCK - 1) / BLOCK;
+    const unsigned g = grid_for(N, bpc);
+    begin_launch();
+#define DICP_BALL(T, KK) ball_query_kernel<T, KK><<<g, BLOCK, 0, st>>>((const T*)x, cx, n, Pn, x_keys, x_perm, y_plans, y_keys, y_perm, \
+        (const V4<T>::type*)y_rows4, m, Pm, N, k, bpc, (T*)d2, idx, counts, (int32_t*)workspace, visited)
+#define DICP_BALL_T(T) do { \
+        switch (ball_kcap(k)) { \
+            case 1: DICP_BALL(T, 1); break; case 4: DICP_BALL(T, 4); break; case 8: DICP_BALL(T, 8); break; \
+            case 16: DICP_BALL(T, 16); break; default: DICP_BALL(T, 32); break; } } while (0)
+    if (dtype == DICP_F32) DICP_BALL_T(float); else DICP_BALL_T(double);
+#undef DICP_BALL_T
+#undef DICP_BALL
+    return launch_status();
+}
+
+int dicp_ball_query_backward(int dtype, const void* g_d2, const void* x, int cx, int n, const void* y_rows4, const int32_t* y_perm, int m, int cy,
+                             int N, int k, const void* fwd_workspace, void* grad_x, void* grad_y, void* stream) {
+    if (!g_d2 || !x || !y_rows4 || !y_perm || !fwd_workspace) return DICP_ERR_NULL;
+    int rc = ball_check(dtype, N, n);
+    if (rc || (rc = ball_check(dtype, N, m))) return rc;
+    if (cx < 3 || cy < 3 || k < 1 || k > BALL_KMAX) return DICP_ERR_SHAPE;
+    const size_t ts = dtype == DICP_F32 ? 4 : 8;
+    if ((uintptr_t)g_d2 % ts || (uintptr_t)x % ts || (uintptr_t)y_rows4 % (4 * ts) || (uintptr_t)y_perm % 4 || (uintptr_t)fwd_workspace % 4 ||
+        (grad_x && (uintptr_t)grad_x % ts) || (grad_y && (uintptr_t)grad_y % ts)) return DICP_ERR_ALIGN;
+    if (!grad_x && !grad_y) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    if (grad_y && (rc = dicp_fill::zero(grad_y, (size_t)N * m * cy * ts, st))) return rc;
+    const int Pm = ball_slots(m);
+    const int bpc = (n + BLOCK - 1) / BLOCK;
+    const unsigned g = grid_for(N, bpc);
+    begin_launch();
+#define DICP_BALL_BWD(T) ball_bwd_kernel<T><<<g, BLOCK, 0, st>>>((const T*)g_d2, (const T*)x, cx, n, (const V4<T>::type*)y_rows4, y_perm, m, Pm, cy, \
+        N, k, bpc, (const int32_t*)fwd_workspace, (T*)grad_x, (T*)grad_y)
+    if (dtype == DICP_F32) DICP_BALL_BWD(float); else DICP_BALL_BWD(double);
+#undef DICP_BALL_BWD
+    return launch_status();
+}

@@ -903,6 +903,33 @@ int dicp_fps_forward(int dtype, const void* pts, int c, const int32_t* rows, con
                      void* out, int64_t* idx, void* dist, int32_t* k_eff, void* workspace, size_t workspace_bytes, void* stream);
 int dicp_fps_backward(int dtype, const void* grad_out, const int64_t* idx, int N, int n, int k, int c, void* grad_pts, void* stream);
 
+/* Fixed-radius neighbours on a sorted cell grid (dicp_amd/ball.py: ball_query; the arithmetic and its proof: csrc/dicp_ball.h).
+ *   pts (N,m,c) T, c >= 3; rows: optional (N) row counts as tgt_rows; radius: ONE T in device memory, finite and > 0 (anything else: a
+ *   grid without rows, no neighbours).  d2 as dicp_knn_points; the candidates of a query are the rows j < rows[b] with three finite
+ *   coordinates and d2 finite, d2 <= r2 = fl(radius * radius), the bound inclusive.
+ * dicp_ball_grid_slots: P, the sorted slots per cloud of m rows (the next power of two, at least 2); 0 for a bad m.
+ * dicp_ball_plan_bytes: the bytes of one cloud's plan (origin, cell edges, key widths, live-row count: all chosen on the device).
+ * dicp_ball_grid_build, order_by = NULL: the grid of every cloud -- plans (N * plan bytes), keys (N,P) the sorted 64-bit cell keys, perm
+ *   (N,P) the row of every sorted slot, rows4 (N,P,4) T the live rows as (x, y, z, 0) in sorted order.  O(m) memory, no host read-back.
+ *   order_by = the plans of another grid: keys / perm order these rows (queries) by the cell of that grid nearest to them (plans and rows4
+ *   must be NULL, radius is not read): the first m sorted slots are the m rows, the ones past rows[b] or with a non-finite coordinate last.
+ * dicp_ball_query_workspace_bytes: the bytes of the search's workspace (the sorted slot of every entry, for the backward); 0 for bad arguments.
+ * dicp_ball_query: x (N,n,cx) T the queries, x_keys / x_perm their order (above), the grid of y.  d2 (N,n,k) T, idx (N,n,k) int64: the first
+ *   min(k, count) candidates in (d2, index) order, +inf / -1 beyond; counts (N,n) int32 exact, never capped by k; all in the original query
+ *   order.  visited: optional (N) rows scanned per cloud (diagnostics).  No float atomics: bit-reproducible.
+ * dicp_ball_query_backward: grad_x (N,n,cx) T = sum_o 2 g_io (x_i - y_idx) in list order, written once (columns 3.. zero); grad_y (N,m,cy) T
+ *   zero-filled by a kernel, then -2 g_io (x_i - y_idx) added to row idx with float atomics.  Either may be NULL. */
+int dicp_ball_grid_slots(int m);
+int dicp_ball_plan_bytes(void);
+int dicp_ball_grid_build(int dtype, const void* pts, int c, const int32_t* rows, int N, int m, const void* radius, const void* order_by,
+                         void* plans, uint64_t* keys, int32_t* perm, void* rows4, void* stream);
+size_t dicp_ball_query_workspace_bytes(int dtype, int N, int n, int k);
+int dicp_ball_query(int dtype, const void* x, int cx, int n, const uint64_t* x_keys, const int32_t* x_perm, const void* y_plans,
+                    const uint64_t* y_keys, const int32_t* y_perm, const void* y_rows4, int m, int N, int k,
+                    void* d2, int64_t* idx, int32_t* counts, void* workspace, size_t workspace_bytes, unsigned long long* visited, void* stream);
+int dicp_ball_query_backward(int dtype, const void* g_d2, const void* x, int cx, int n, const void* y_rows4, const int32_t* y_perm, int m, int cy,
+                             int N, int k, const void* fwd_workspace, void* grad_x, void* grad_y, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
