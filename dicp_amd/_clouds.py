@@ -1,0 +1,129 @@
+"""The cloud arguments of the point-cloud operators (normals, voxel, knn, fps, ball): one cloud, a padded batch with row counts, or a list.
+
+check / check_pair validate on the host (no device is touched), place moves a checked batch to the compute device, restore cuts the
+library's (N, ...) results back to the caller's form and device.  What differs between the operators is an argument at their call site.
+"""
+import torch
+
+from ._ops import _DT, compute_device
+
+ROW, SLOT, CLOUD, VOXEL = "row", "slot", "cloud", "voxel"      # how restore cuts an output: see there
+
+
+def _err(what, msg):
+    raise ValueError("%s: %s" % (what, msg))
+
+
+def _check_k(k, what, lo, hi):
+    if isinstance(k, bool) or not isinstance(k, int) or not (lo <= k <= hi):
+        _err(what, "k must be an int in [%d, %d], got %r" % (lo, hi, k))
+
+
+def _check_points(t, name, what):
+    if not isinstance(t, torch.Tensor):
+        _err(what, "%s must be a tensor, got %s" % (name, type(t).__name__))
+    if t.dtype not in _DT:
+        _err(what, "%s must be float32 or float64, got %s" % (name, t.dtype))
+    if t.dim() < 1 or t.shape[-1] < 3:
+        _err(what, "%s needs at least 3 columns (x, y, z), got shape %s" % (name, tuple(t.shape)))
+
+
+def check(t, rows, what, name="points", rows_name="rows", empty_ok=False, flat_rows=False):
+    """-> (form, batch (N,m,c), rows or None, lengths of a list or None); ValueError for anything invalid.
+
+    empty_ok: clouds without rows are let through (place pads them).  flat_rows: rows may have any shape with N elements, a single cloud
+    (N = 1) included; otherwise they are 1-D and need a padded batch."""
+    if isinstance(t, (list, tuple)):
+        if not t:
+            _err(what, "%s is an empty list" % name)
+        for i, c in enumerate(t):
+            _check_points(c, "%s[%d]" % (name, i), what)
+            if c.dim() != 2:
+                _err(what, "%s[%d] must be (m_b, c), got shape %s" % (name, i, tuple(c.shape)))
+        if len({c.shape[1] for c in t}) != 1 or len({c.dtype for c in t}) != 1 or len({c.device for c in t}) != 1:
+            _err(what, "the clouds of %s need one column count, dtype and device" % name)
+        if rows is not None:
+            _err(what, "%s is a list: %s come from the list itself" % (name, rows_name))
+        lens = [c.shape[0] for c in t]
+        form, batch, rows = "list", torch.nn.utils.rnn.pad_sequence(list(t), batch_first=True), torch.tensor(lens, dtype=torch.int32)
+    else:
+        _check_points(t, name, what)
+        if t.dim() not in (2, 3):
+            _err(what, "%s must be (m, c), (N, m, c) or a list of (m_b, c), got shape %s" % (name, tuple(t.shape)))
+        if t.dim() == 2 and rows is not None and not flat_rows:
+            _err(what, "%s needs a padded batch (N, m, c)" % rows_name)
+        form, batch, lens = ("single", t.unsqueeze(0), None) if t.dim() == 2 else ("batch", t, None)
+    N, m = batch.shape[0], batch.shape[1]
+    if N < 1 or (m < 1 and not empty_ok):
+        _err(what, "%s is an empty batch, shape %s" % (name, tuple(batch.shape)))
+    if lens is None and rows is not None:
+        rows = torch.as_tensor(rows)
+        if rows.dtype.is_floating_point or rows.dtype.is_complex or rows.dtype == torch.bool or rows.numel() != N \
+                or not (flat_rows or rows.dim() == 1):
+            _err(what, "%s must be %d integer counts" % (rows_name, N))
+        if not rows.is_cuda and (int(rows.min()) < 0 or int(rows.max()) > m):
+            _err(what, "%s must lie in [0, %d]" % (rows_name, m))
+    return form, batch, rows, lens
+
+
+def check_pair(x, y, x_rows, y_rows, what):
+    """check on both arguments of a two-cloud operator (either side may be empty), and that they go together -> (check(x), check(y))"""
+    cx = check(x, x_rows, what, "x", "x_rows", empty_ok=True)
+    cy = check(y, y_rows, what, "y", "y_rows", empty_ok=True)
+    bx, by = cx[1], cy[1]
+    if cx[0] != cy[0]:
+        _err(what, "x and y must have the same form (single clouds, padded batches or lists), got %s and %s" % (cx[0], cy[0]))
+    if bx.dtype != by.dtype:
+        _err(what, "x and y must have one dtype, got %s and %s" % (bx.dtype, by.dtype))
+    if bx.device != by.device:
+        _err(what, "x and y must be on one device, got %s and %s" % (bx.device, by.device))
+    if bx.shape[0] != by.shape[0]:
+        _err(what, "x and y must hold the same number of clouds, got %d and %d" % (bx.shape[0], by.shape[0]))
+    return cx, cy
+
+
+def place(batch, rows, xyz=False):
+    """A checked batch and its rows on the compute device -> (on_cpu, batch (N,m',c') contiguous, rows (N,) int32 or None).
+
+    xyz: only columns 0:3 go to the library unless there are 3 or 6.  A batch without rows is padded to one row with a row count of 0."""
+    on_cpu = not batch.is_cuda
+    dev = compute_device() if on_cpu else batch.device
+    b = batch.to(dev)
+    if xyz and b.shape[2] not in (3, 6):
+        b = b[..., :3]
+    if b.shape[1] == 0:                                     # the library needs a row: one pad row, no row taking part
+        b = torch.zeros((b.shape[0], 1, b.shape[2]), dtype=b.dtype, device=dev) + b.sum() * 0
+        rows = torch.zeros(b.shape[0], dtype=torch.int32)
+    if rows is not None:
+        rows = rows.to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+    return on_cpu, b.contiguous(), rows
+
+
+def pair(x, y, x_rows, y_rows, what):
+    """check_pair, then place with xyz on both -> (form, on_cpu, lens_x, n, m, x (N,n',c), y (N,m',c), x_rows, y_rows) with n', m' >= 1"""
+    (form, bx, rx, lx), (_, by, ry, _) = check_pair(x, y, x_rows, y_rows, what)
+    on_cpu, bx_d, rx_d = place(bx, rx, xyz=True)
+    _, by_d, ry_d = place(by, ry, xyz=True)
+    return form, on_cpu, lx, bx.shape[1], by.shape[1], bx_d, by_d, rx_d, ry_d
+
+
+def restore(form, on_cpu, n, lens, outs, k=None, voxels=None):
+    """The library's results in the caller's form, on the caller's device -> a tuple with one entry per output.
+
+    outs: [(kind, tensor (N, ...))].  ROW: one entry per input row, cut to the cloud's n / lens[b] rows; SLOT: k slots, a list's cut to
+    min(k, lens[b]); CLOUD: one value per cloud; VOXEL: one entry per voxel, cut to voxels[b].  A single cloud gets cloud 0 of each, a
+    list one tensor per cloud, a batch the tensors themselves."""
+    if on_cpu:
+        outs = [(kind, t.cpu()) for kind, t in outs]
+
+    def cut(kind, t, b, rows):
+        if kind == CLOUD:
+            return t[b]
+        if kind == SLOT:
+            return t[b, :min(k, rows)] if form == "list" else t[b]
+        return t[b, :(rows if kind == ROW else int(voxels[b]))]
+    if form == "list":
+        return tuple([cut(kind, t, b, lens[b]) for b in range(len(lens))] for kind, t in outs)
+    if form == "single":
+        return tuple(cut(kind, t, 0, n) for kind, t in outs)
+    return tuple(t[:, :n] if kind == ROW and t.shape[1] != n else t for kind, t in outs)

@@ -72,6 +72,12 @@ def _p(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
+def _workspace(nbytes, device):
+    """nbytes (or more) of uint8 on the device, starting at a multiple of 256 bytes"""
+    buf = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)
+    return buf[(-buf.data_ptr()) % 256:]                    # (the caching allocator's blocks are aligned already)
+
+
 class _NoSwitch:
     def __enter__(self):
         return None

@@ -11,9 +11,10 @@ import math
 
 import torch
 
-from . import _lib
+from . import _clouds, _lib
+from ._clouds import ROW
 from ._ops import _DT, _p, _stream, _on
-from .knn import _check_k, _err, _inputs
+from .knn import K_MIN, K_MAX
 
 
 class CellGrid:
@@ -94,6 +95,10 @@ class _BallQuery(torch.autograd.Function):
         return (gx, gy) + nothing[2:]
 
 
+def _err(msg):
+    raise ValueError(msg)
+
+
 def _check_radius(radius):
     """-> a Python float (checked: finite and > 0) or a 0-d device tensor (not read back: see ball_query)"""
     if isinstance(radius, torch.Tensor):
@@ -145,14 +150,14 @@ def ball_query(x, y, radius, k=16, x_rows=None, y_rows=None, return_counts=False
     only the cells its ball can touch.  Nothing is read back from the device: with device tensors and device (or no) row counts a call
     is kernels only.
     """
-    _check_k(k, "ball_query")
+    _clouds._check_k(k, "ball_query", K_MIN, K_MAX)
     radius = _check_radius(radius)
     first = x[0] if isinstance(x, (list, tuple)) and x else x
     if isinstance(radius, float) and isinstance(first, torch.Tensor) and first.dtype in _DT:
         r_t = float(torch.tensor(radius, dtype=first.dtype))
         if not (math.isfinite(r_t) and r_t > 0.0):
             _err("ball_query: radius must be finite and > 0 in %s, got %r" % (first.dtype, radius))
-    form, on_cpu, lens, n, _, xb, yb, rx, ry = _inputs(x, y, x_rows, y_rows, "ball_query")
+    form, on_cpu, lens, n, _, xb, yb, rx, ry = _clouds.pair(x, y, x_rows, y_rows, "ball_query")
     if isinstance(radius, torch.Tensor):
         r_d = radius.detach().to(device=xb.device, dtype=xb.dtype).reshape(1)
     else:
@@ -160,12 +165,4 @@ def ball_query(x, y, radius, k=16, x_rows=None, y_rows=None, return_counts=False
     grid = CellGrid(yb.detach(), ry, r_d)
     xkeys, xperm = grid.order(xb.detach(), rx)
     d2, idx, counts = _BallQuery.apply(xb, yb, grid, xkeys, xperm, k, _visited)
-    d2, idx, counts = d2[:, :n], idx[:, :n], counts[:, :n]
-    if on_cpu:
-        d2, idx, counts = d2.cpu(), idx.cpu(), counts.cpu()
-    outs = (d2, idx, counts) if return_counts else (d2, idx)
-    if form == "list":
-        return tuple([o[b, :lens[b]] for b in range(len(lens))] for o in outs)
-    if form == "single":
-        return tuple(o[0] for o in outs)
-    return outs
+    return _clouds.restore(form, on_cpu, n, lens, [(ROW, d2), (ROW, idx)] + ([(ROW, counts)] if return_counts else []))

@@ -32,7 +32,6 @@ namespace {
 constexpr int BALL_KMAX = 32;
 constexpr int BALL_CHUNK = 2048;                        // pairs a workgroup sorts in LDS: 24 KiB
 
-inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 inline int ball_slots(int m) { int p = 2; while (p < m) p <<= 1; return p; }
 
 template <typename T>
@@ -209,12 +208,7 @@ __global__ __launch_bounds__(BLOCK) void ball_query_kernel(const T* __restrict__
             slots[o0 + o] = sl[i];
         }
     }
-    if (visited) {                                          // diagnostics: rows visited, one atomic per wave
-        unsigned long long t = steps;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) t += __shfl_xor(t, off);
-        if ((threadIdx.x & (WAVE - 1)) == 0 && t) atomicAdd(visited + b, t);
-    }
+    if (visited) wave_add(visited + b, steps);          // diagnostics: rows visited, one atomic per wave
 }
 
 template <typename T>
@@ -254,18 +248,11 @@ __global__ __launch_bounds__(BLOCK) void ball_bwd_kernel(const T* __restrict__ g
     }
 }
 
-inline int ball_kcap(int k) { return k == 1 ? 1 : (k <= 4 ? 4 : (k <= 8 ? 8 : (k <= 16 ? 16 : 32))); }
-
 int ball_check(int dtype, int N, int m) {
     if (bad_dtype(dtype)) return DICP_ERR_DTYPE;
     if (N <= 0 || m <= 0 || m > (1 << 30)) return DICP_ERR_SHAPE;
     if ((size_t)N * ball_slots(m) > ((size_t)1 << 40)) return DICP_ERR_SHAPE;
     return 0;
-}
-
-inline unsigned grid_items(size_t n) {
-    const size_t g = (n + BLOCK - 1) / BLOCK;
-    return (unsigned)(g < 1 ? 1 : (g > 65536 ? 65536 : g));
 }
 
 int ball_sort(uint64_t* key, int32_t* idx, int N, int P, hipStream_t st) {
@@ -274,7 +261,7 @@ int ball_sort(uint64_t* key, int32_t* idx, int N, int P, hipStream_t st) {
     if (chunks > 0x7fffffffu) return DICP_ERR_SHAPE;
     ball_sort_local<<<(unsigned)chunks, BLOCK, 0, st>>>(key, idx, P, chunk, 2, chunks);
     for (int k = chunk << 1; k <= P && k > 0; k <<= 1) {
-        for (int j = k >> 1; j >= chunk; j >>= 1) ball_sort_global<<<grid_items(pairs), BLOCK, 0, st>>>(key, idx, P, k, j, pairs);
+        for (int j = k >> 1; j >= chunk; j >>= 1) ball_sort_global<<<grid_1d(pairs), BLOCK, 0, st>>>(key, idx, P, k, j, pairs);
         ball_sort_local<<<(unsigned)chunks, BLOCK, 0, st>>>(key, idx, P, chunk, k, chunks);
     }
     return 0;
@@ -302,9 +289,9 @@ int dicp_ball_grid_build(int dtype, const void* pts, int c, const int32_t* rows,
     begin_launch();
 #define DICP_BALL_BUILD(T) do { \
         if (!order_by) ball_plan_kernel<T><<<N, BLOCK, 0, st>>>((const T*)pts, c, rows, m, (const T*)radius, plans); \
-        ball_keys_kernel<T><<<grid_items(total), BLOCK, 0, st>>>((const T*)pts, c, rows, N, m, P, pl, order_by ? 0 : 1, keys, perm); \
+        ball_keys_kernel<T><<<grid_1d(total), BLOCK, 0, st>>>((const T*)pts, c, rows, N, m, P, pl, order_by ? 0 : 1, keys, perm); \
         if ((rc = ball_sort(keys, perm, N, P, st))) return rc; \
-        if (!order_by) ball_pack_kernel<T><<<grid_items(total), BLOCK, 0, st>>>((const T*)pts, c, N, m, P, plans, perm, (V4<T>::type*)rows4); \
+        if (!order_by) ball_pack_kernel<T><<<grid_1d(total), BLOCK, 0, st>>>((const T*)pts, c, N, m, P, plans, perm, (V4<T>::type*)rows4); \
     } while (0)
     if (dtype == DICP_F32) DICP_BALL_BUILD(float); else DICP_BALL_BUILD(double);
 #undef DICP_BALL_BUILD
@@ -336,7 +323,7 @@ int dicp_ball_query(int dtype, const void* x, int cx, int n, const uint64_t* x_k
 #define DICP_BALL(T, KK) ball_query_kernel<T, KK><<<g, BLOCK, 0, st>>>((const T*)x, cx, n, Pn, x_keys, x_perm, y_plans, y_keys, y_perm, \
         (const V4<T>::type*)y_rows4, m, Pm, N, k, bpc, (T*)d2, idx, counts, (int32_t*)workspace, visited)
 #define DICP_BALL_T(T) do { \
-        switch (ball_kcap(k)) { \
+        switch (topk_kcap(k)) { \
             case 1: DICP_BALL(T, 1); break; case 4: DICP_BALL(T, 4); break; case 8: DICP_BALL(T, 8); break; \
             case 16: DICP_BALL(T, 16); break; default: DICP_BALL(T, 32); break; } } while (0)
     if (dtype == DICP_F32) DICP_BALL_T(float); else DICP_BALL_T(double);

@@ -87,6 +87,14 @@ __device__ __forceinline__ T score(const T* nx, const T4& y) {
     return fma_t(nx[0], y.x, fma_t(nx[1], y.y, fma_t(nx[2], y.z, y.w)));
 }
 
+// ------------------------------------------------------------------- shared by the point-cloud operators' kernels
+// A diagnostic counter: the wave's sum of t, added to *total by one lane (no atomic for a zero sum)
+__device__ __forceinline__ void wave_add(unsigned long long* total, unsigned long long t) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) t += __shfl_xor(t, off);
+    if ((threadIdx.x & (WAVE - 1)) == 0 && t) atomicAdd(total, t);
+}
+
 // ------------------------------------------------------------------- host helpers
 // hipGetLastError() is sticky per host thread and the HIP runtime is shared with PyTorch, which can
 // leave an unrelated error behind: every entry point clears it (begin_launch) before launching and
@@ -97,6 +105,13 @@ inline int launch_status() {
     return e == hipSuccess ? 0 : -(int)e;
 }
 inline bool bad_dtype(int d) { return d != DICP_F32 && d != DICP_F64; }
+
+inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
+// blocks of a grid-stride kernel over n items: one thread each, at least 1 and at most 65536 blocks
+inline unsigned grid_1d(size_t n) {
+    const size_t g = (n + BLOCK - 1) / BLOCK;
+    return (unsigned)(g < 1 ? 1 : (g > 65536 ? 65536 : g));
+}
 
 struct Rows { const int32_t* src; const int32_t* tgt; };     // optional per-cloud row counts of a ragged batch
 

@@ -58,6 +58,12 @@ DICP_HD void topk_init(T (&d)[K], int (&id)[K], int (&sl)[K], int k) {
     for (int i = 0; i < K; ++i) { d[i] = i < K - k ? -inf : inf; id[i] = -1; sl[i] = -1; }
 }
 
+// The list capacities the kernels are instantiated for: the smallest of 1, 4, 8, 16, 32 that holds k
+inline int topk_kcap(int k) { return k == 1 ? 1 : (k <= 4 ? 4 : (k <= 8 ? 8 : (k <= 16 ? 16 : 32))); }
+
+// (The write-out of entries K - k .. K - 1 stays an inline loop in the three kernels: as a helper taking a per-entry callable it cost
+// normals_knn_kernel<double, 16 / 32> and every ball_query_kernel 2 to 5 VGPRs, and ball_query_kernel<float, 8 / 32> a wave of occupancy.)
+
 // The insertion as a callable ins(d2, j): row j of the sorted cloud at distance d2; orig(j) its original index, read only when d2 can
 // enter.  (A lambda, not a forced-inline function: inlined by the optimiser in its own time, the walk kernels keep the registers of the
 // hand-written form -- forced in early, 50 % more VGPRs at K = 32.)

@@ -32,7 +32,6 @@ template <> struct FpsR<double> { static constexpr int v = FPS_R64; };
 
 inline int fps_resident_rows(int dtype) { return FPS_THREADS * (dtype == DICP_F32 ? FPS_R32 : FPS_R64); }
 inline int fps_groups(int n) { return (n + FPS_STREAM_ROWS - 1) / FPS_STREAM_ROWS; }
-inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 __device__ __forceinline__ FpsKey<float> key_shfl_xor(const FpsKey<float>& a, int off) {
     FpsKey<float> r;

@@ -39,8 +39,6 @@ template <typename T> struct BwdRows;                   // y-gradient window row
 template <> struct BwdRows<float>  { static constexpr int v = BLOCK + 2 * 1024; };
 template <> struct BwdRows<double> { static constexpr int v = BLOCK + 2 * 512; };
 
-inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 template <typename T, int K>
 __global__ __launch_bounds__(BLOCK) void knn_points_kernel(const typename V4<T>::type* __restrict__ xgs4, const int32_t* __restrict__ xperm,
                                                            const int32_t* __restrict__ x_rows, int n, int n_pad,
@@ -98,12 +96,7 @@ __global__ __launch_bounds__(BLOCK) void knn_points_kernel(const typename V4<T>:
         const size_t o0 = ((size_t)b * n + s) * k;
         for (int o = 0; o < k; ++o) { d2_out[o0 + o] = inf_v<T>(); idx_out[o0 + o] = -1; }
     }
-    if (walked) {                                           // diagnostics: rows walked, one atomic per wave
-        unsigned long long t = steps;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) t += __shfl_xor(t, off);
-        if ((threadIdx.x & (WAVE - 1)) == 0 && t) atomicAdd(walked + b, t);
-    }
+    if (walked) wave_add(walked + b, steps);          // diagnostics: rows walked, one atomic per wave
 }
 
 template <typename T>
@@ -177,8 +170,6 @@ __global__ __launch_bounds__(BLOCK) void knn_points_bwd_kernel(const T* __restri
     }
 }
 
-inline int knn_kcap(int k) { return k == 1 ? 1 : (k <= 4 ? 4 : (k <= 8 ? 8 : (k <= 16 ? 16 : 32))); }
-
 int knn_check(int dtype, int N, int n, int m, int k) {
     if (bad_dtype(dtype)) return DICP_ERR_DTYPE;
     if (N <= 0 || n <= 0 || m <= 0 || k < 1 || k > KNN_KMAX) return DICP_ERR_SHAPE;
@@ -216,7 +207,7 @@ int dicp_knn_points(int dtype, const void* x_tgs4, const int32_t* x_perm, const 
 #define DICP_KNN(T, KK) knn_points_kernel<T, KK><<<g, BLOCK, 0, st>>>((const V4<T>::type*)x_tgs4, x_perm, x_rows, n, n_pad, (const T*)y_keys, \
         (const V4<T>::type*)y_tgs4, y_perm, y_rows, m, m_pad, N, k, bpc, (T*)d2, idx, slots, walked)
 #define DICP_KNN_T(T) do { \
-        switch (knn_kcap(k)) { \
+        switch (topk_kcap(k)) { \
             case 1: DICP_KNN(T, 1); break; case 4: DICP_KNN(T, 4); break; case 8: DICP_KNN(T, 8); break; \
             case 16: DICP_KNN(T, 16); break; default: DICP_KNN(T, 32); break; } } while (0)
     if (dtype == DICP_F32) DICP_KNN_T(float); else DICP_KNN_T(double);

@@ -36,7 +36,6 @@ template <typename T> struct NrmTau;
 template <> struct NrmTau<float>  { static constexpr double v = 1e-6; };
 template <> struct NrmTau<double> { static constexpr double v = 1e-12; };
 
-inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // The forward workspace, in this order (each part 256-byte aligned); the backward reads tperm / tgs4 / nbr_s of it
 struct NrmLayout {
@@ -109,12 +108,7 @@ __global__ __launch_bounds__(BLOCK) void normals_knn_kernel(const typename V4<T>
     } else if (s < m && nbr_out) {                          // the row s of the cloud's padding (original order)
         for (int o = 0; o < k; ++o) nbr_out[((size_t)b * m + s) * k + o] = -1;
     }
-    if (walked) {                                           // diagnostics: rows walked, one atomic per wave
-        unsigned long long t = steps;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) t += __shfl_xor(t, off);
-        if ((threadIdx.x & (WAVE - 1)) == 0 && t) atomicAdd(walked + b, t);
-    }
+    if (walked) wave_add(walked + b, steps);          // diagnostics: rows walked, one atomic per wave
 }
 
 // ------------------------------------------------------------------ per-point eigen-system (forward and backward)
@@ -226,8 +220,6 @@ __global__ __launch_bounds__(BLOCK) void normals_bwd_kernel(const typename V4<T>
     }
 }
 
-inline int nrm_kcap(int k) { return k <= 8 ? 8 : (k <= 16 ? 16 : 32); }
-
 int nrm_check(int dtype, int N, int m, int k, int vp_per_cloud) {
     if (bad_dtype(dtype)) return DICP_ERR_DTYPE;
     if (N <= 0 || m <= 0 || k < 3 || k > NRM_KMAX || (vp_per_cloud != 0 && vp_per_cloud != 1)) return DICP_ERR_SHAPE;
@@ -279,7 +271,7 @@ int dicp_normals_forward(int dtype, const void* pts, int c, const int32_t* rows,
     begin_launch();
 #define DICP_NRM_KNN(T, KK) normals_knn_kernel<T, KK><<<g, BLOCK, 0, st>>>((const V4<T>::type*)(ws + L.tgs4), tperm, rows, N, m, m_pad, k, bpc, nbr_s, neighbors, walked)
 #define DICP_NRM(T) do { \
-        const int kc = nrm_kcap(k); \
+        const int kc = topk_kcap(k < 8 ? 8 : k);   /* (no list below 8) */ \
         if (kc == 8) DICP_NRM_KNN(T, 8); else if (kc == 16) DICP_NRM_KNN(T, 16); else DICP_NRM_KNN(T, 32); \
         normals_point_kernel<T><<<g, BLOCK, 0, st>>>((const V4<T>::type*)(ws + L.tgs4), tperm, rows, N, m, m_pad, k, bpc, nbr_s, (const T*)viewpoint, vs, \
                                                       (T*)normals, (T*)curvature); } while (0)

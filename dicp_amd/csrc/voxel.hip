@@ -40,7 +40,6 @@ constexpr int VOX_BIG_BLOCKS = 1024;
 enum { CI_NV = 0, CI_PASSES = 1, CI_WY = 2, CI_WZ = 3, CI_V = 4, CI_OUT = 5, CI_ERR = 6, VOX_CI = 8 };
 enum { VOX_ERR_RANGE = 1, VOX_ERR_BITS = 2 };
 
-inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 inline int vox_tiles(int m) { return (m + VOX_TILE - 1) / VOX_TILE; }
 inline size_t vox_big_cap(int N, int m) { return (size_t)N * m / (VOX_SMALL + 1) + 1; }
 
@@ -603,11 +602,6 @@ int vox_check(int dtype, int N, int m, int c) {
     return 0;
 }
 
-inline unsigned grid_rows(size_t n) {
-    const size_t g = (n + BLOCK - 1) / BLOCK;
-    return (unsigned)(g < 1 ? 1 : (g > 65536 ? 65536 : g));
-}
-
 }  // namespace
 
 size_t dicp_voxel_workspace_bytes(int dtype, int N, int m, int c) {
@@ -684,7 +678,7 @@ int dicp_voxel_reduce(int dtype, const void* pts, int c, int N, int m, int M, co
     const char* ws = (const char*)workspace;
     const size_t rows_total = (size_t)N * m;
     begin_launch();
-    vox_fill_inverse_kernel<<<grid_rows(rows_total), BLOCK, 0, st>>>(inverse, rows_total);
+    vox_fill_inverse_kernel<<<grid_1d(rows_total), BLOCK, 0, st>>>(inverse, rows_total);
     if ((rc = launch_status())) return rc;
     if (M == 0) return 0;
     if ((rc = dicp_fill::zero(centroids, (size_t)N * M * c * ts, st))) return rc;

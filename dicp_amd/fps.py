@@ -13,8 +13,9 @@ captured region (dicp_amd.graphed); a list, CPU rows / start tensors and start="
 """
 import torch
 
-from . import _lib
-from ._ops import _DT, _p, _stream, _on, compute_device
+from . import _clouds, _lib
+from ._clouds import SLOT, CLOUD
+from ._ops import _DT, _p, _stream, _on, _workspace
 
 T = 1024                                                    # threads of the resident workgroup (one per cloud)
 NR = {torch.float32: 16 * T, torch.float64: 8 * T}          # the largest cloud of the resident form: 16 / 8 rows a thread in registers
@@ -46,10 +47,7 @@ class _Fps(torch.autograd.Function):
         dist = torch.empty((N, k), dtype=pts.dtype, device=dev)
         keff = torch.empty(N, dtype=torch.int32, device=dev)
         ws_bytes = lib.dicp_fps_workspace_bytes(dt, N, n, k, form)
-        ws = None
-        if ws_bytes:
-            buf = torch.empty(ws_bytes + 256, dtype=torch.uint8, device=dev)
-            ws = buf[(-buf.data_ptr()) % 256:]
+        ws = _workspace(ws_bytes, dev) if ws_bytes else None
         with _on(dev):
             _lib.check(lib.dicp_fps_forward(dt, _p(pts), c, _p(rows), _p(start), N, n, k, form, _p(out), _p(idx), _p(dist), _p(keff),
                                             _p(ws), ws_bytes, _stream()), "dicp_fps_forward")
@@ -69,49 +67,6 @@ class _Fps(torch.autograd.Function):
 
 def _err(msg):
     raise ValueError("sample_farthest_points: " + msg)
-
-
-def _check_points(t, name):
-    if not isinstance(t, torch.Tensor):
-        _err("%s must be a tensor, got %s" % (name, type(t).__name__))
-    if t.dtype not in _DT:
-        _err("%s must be float32 or float64, got %s" % (name, t.dtype))
-    if t.dim() < 1 or t.shape[-1] < 3:
-        _err("%s needs at least 3 columns (x, y, z), got shape %s" % (name, tuple(t.shape)))
-
-
-def _batch(points, rows):
-    """-> (form, (N,n,c) batch, rows or None, lengths of a list or None); ValueError for anything invalid"""
-    if isinstance(points, (list, tuple)):
-        if not points:
-            _err("points is an empty list")
-        for i, c in enumerate(points):
-            _check_points(c, "points[%d]" % i)
-            if c.dim() != 2:
-                _err("points[%d] must be (n_b, c), got shape %s" % (i, tuple(c.shape)))
-        if len({c.shape[1] for c in points}) != 1 or len({c.dtype for c in points}) != 1 or len({c.device for c in points}) != 1:
-            _err("the clouds of a list need one column count, dtype and device")
-        if rows is not None:
-            _err("points is a list: its row counts come from the list itself")
-        lens = [c.shape[0] for c in points]
-        return "list", torch.nn.utils.rnn.pad_sequence(list(points), batch_first=True), torch.tensor(lens, dtype=torch.int32), lens
-    _check_points(points, "points")
-    if points.dim() == 2:
-        if rows is not None:
-            _err("rows needs a padded batch (N, n, c)")
-        return "single", points.unsqueeze(0), None, None
-    if points.dim() != 3:
-        _err("points must be (n, c), (N, n, c) or a list of (n_b, c), got shape %s" % (tuple(points.shape),))
-    if points.shape[0] < 1:
-        _err("empty batch")
-    if rows is not None:
-        r = torch.as_tensor(rows)
-        if r.dtype.is_floating_point or r.dtype.is_complex or r.dtype == torch.bool or r.dim() != 1 or r.numel() != points.shape[0]:
-            _err("rows must be %d integer counts" % points.shape[0])
-        if not r.is_cuda and (int(r.min()) < 0 or int(r.max()) > points.shape[1]):
-            _err("rows must lie in [0, %d]" % points.shape[1])
-        rows = r
-    return "batch", points, rows, None
 
 
 def _start(start, N):
@@ -172,31 +127,18 @@ def sample_farthest_points(points, k, rows=None, start=0, return_rows=False, ret
         _err("k must be an int >= 1, got %r" % (k,))
     if _form not in _FORMS:
         _err("_form must be None, \"resident\" or \"streamed\", got %r" % (_form,))
-    form, batch, rows, lens = _batch(points, rows)
-    N, n, c = batch.shape
+    form, batch, rows, lens = _clouds.check(points, rows, "sample_farthest_points", empty_ok=True)
+    N, n = batch.shape[0], batch.shape[1]
     if _form == "resident" and n > NR[batch.dtype]:
         _err("the resident form holds at most %d rows of %s, got %d" % (NR[batch.dtype], batch.dtype, n))
     start_t = _start(start, N)
 
-    on_cpu = not batch.is_cuda
-    dev = compute_device() if on_cpu else batch.device
-    x = batch.to(dev)
-    if n == 0:                                              # the library needs a row: one pad row, no row taking part
-        x = torch.zeros((N, 1, c), dtype=x.dtype, device=dev) + x.sum() * 0
-        rows = torch.zeros(N, dtype=torch.int32)
-    x = x.contiguous()
-    rows_d = rows.to(device=dev, dtype=torch.int32).contiguous() if rows is not None else None
+    on_cpu, x, rows_d = _clouds.place(batch, rows)
+    dev = x.device
     if isinstance(start_t, int):                            # (filled on the device: no host-to-device copy)
         start_d = torch.full((N,), start_t, dtype=torch.int64, device=dev)
     else:
         start_d = start_t.to(device=dev).contiguous() if start_t is not None else None
     pts, idx, keff, dist = _Fps.apply(x, rows_d, start_d, k, _FORMS[_form])
-    outs = [pts, idx] + ([keff] if return_rows else []) + ([dist] if return_distances else [])
-    if on_cpu:
-        outs = [o.cpu() for o in outs]
-    if form == "list":
-        kinds = ["slots", "slots"] + (["count"] if return_rows else []) + (["slots"] if return_distances else [])
-        return tuple([o[b] if kind == "count" else o[b, :min(k, lens[b])] for b in range(N)] for kind, o in zip(kinds, outs))
-    if form == "single":
-        outs = [o[0] for o in outs]
-    return tuple(outs)
+    outs = [(SLOT, pts), (SLOT, idx)] + ([(CLOUD, keff)] if return_rows else []) + ([(SLOT, dist)] if return_distances else [])
+    return _clouds.restore(form, on_cpu, n, lens, outs, k=k)

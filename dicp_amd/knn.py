@@ -9,8 +9,9 @@ Exact results on the GPU (libdicp_hip.so: dicp_knn_points / dicp_knn_points_back
 
 import torch
 
-from . import _lib
-from ._ops import _DT, _p, _stream, _on, compute_device
+from . import _clouds, _lib
+from ._clouds import ROW
+from ._ops import _DT, _p, _stream, _on
 
 K_MIN, K_MAX = 1, 32
 REDUCTIONS = ("mean", "sum", "none")
@@ -85,90 +86,6 @@ class _KnnPoints(torch.autograd.Function):
         return gx, gy, None, None, None
 
 
-def _err(msg):
-    raise ValueError(msg)
-
-
-def _check_k(k, what):
-    if isinstance(k, bool) or not isinstance(k, int) or not (K_MIN <= k <= K_MAX):
-        _err("%s: k must be an int in [%d, %d], got %r" % (what, K_MIN, K_MAX, k))
-
-
-def _check_points(t, name, what):
-    if not isinstance(t, torch.Tensor):
-        _err("%s: %s must be a tensor, got %s" % (what, name, type(t).__name__))
-    if t.dtype not in _DT:
-        _err("%s: %s must be float32 or float64, got %s" % (what, name, t.dtype))
-    if t.dim() < 1 or t.shape[-1] < 3:
-        _err("%s: %s needs at least 3 columns (x, y, z), got shape %s" % (what, name, tuple(t.shape)))
-
-
-def _batch(t, rows, name, what):
-    """-> (form, (N,m,c) batch, rows or None, lengths of a list or None); ValueError for anything invalid"""
-    if isinstance(t, (list, tuple)):
-        if not t:
-            _err("%s: %s is an empty list" % (what, name))
-        for i, c in enumerate(t):
-            _check_points(c, "%s[%d]" % (name, i), what)
-            if c.dim() != 2:
-                _err("%s: %s[%d] must be (m_b, c), got shape %s" % (what, name, i, tuple(c.shape)))
-        if len({c.shape[1] for c in t}) != 1 or len({c.dtype for c in t}) != 1 or len({c.device for c in t}) != 1:
-            _err("%s: the clouds of %s need one column count, dtype and device" % (what, name))
-        if rows is not None:
-            _err("%s: %s is a list: its row counts come from the list itself" % (what, name))
-        lens = [c.shape[0] for c in t]
-        batch = torch.nn.utils.rnn.pad_sequence(list(t), batch_first=True)
-        return "list", batch, torch.tensor(lens, dtype=torch.int32), lens
-    _check_points(t, name, what)
-    if t.dim() == 2:
-        if rows is not None:
-            _err("%s: %s_rows needs a padded batch (N, m, c)" % (what, name))
-        return "single", t.unsqueeze(0), None, None
-    if t.dim() != 3:
-        _err("%s: %s must be (m, c), (N, m, c) or a list of (m_b, c), got shape %s" % (what, name, tuple(t.shape)))
-    if rows is not None:
-        r = torch.as_tensor(rows)
-        if r.dtype.is_floating_point or r.dtype.is_complex or r.dtype == torch.bool or r.dim() != 1 or r.numel() != t.shape[0]:
-            _err("%s: %s_rows must be %d integer counts" % (what, name, t.shape[0]))
-        if not r.is_cuda and r.numel() and (int(r.min()) < 0 or int(r.max()) > t.shape[1]):
-            _err("%s: %s_rows must lie in [0, %d]" % (what, name, t.shape[1]))
-        rows = r
-    return "batch", t, rows, None
-
-
-def _inputs(x, y, x_rows, y_rows, what):
-    """Validates both arguments (before any device work) and moves them to the device: -> (form, on_cpu, lens_x, n, m, x (N,n',c), y (N,m',c),
-    x_rows, y_rows) with n', m' >= 1 (an empty side is padded to one row with a row count of 0) and c in {3, 6}."""
-    fx, bx, rx, lx = _batch(x, x_rows, "x", what)
-    fy, by, ry, ly = _batch(y, y_rows, "y", what)
-    if fx != fy:
-        _err("%s: x and y must have the same form (single clouds, padded batches or lists), got %s and %s" % (what, fx, fy))
-    if bx.dtype != by.dtype:
-        _err("%s: x and y must have one dtype, got %s and %s" % (what, bx.dtype, by.dtype))
-    if bx.device != by.device:
-        _err("%s: x and y must be on one device, got %s and %s" % (what, bx.device, by.device))
-    if bx.shape[0] != by.shape[0]:
-        _err("%s: x and y must hold the same number of clouds, got %d and %d" % (what, bx.shape[0], by.shape[0]))
-    if bx.shape[0] < 1:
-        _err("%s: empty batch" % what)
-    on_cpu = not bx.is_cuda
-    dev = compute_device() if on_cpu else bx.device
-
-    def put(b, r):
-        b = b.to(dev)
-        if b.shape[-1] not in (3, 6):
-            b = b[..., :3]
-        N, m = b.shape[0], b.shape[1]
-        if m == 0:                                      # the library needs a row: one pad row, no row taking part
-            b = torch.zeros((N, 1, b.shape[2]), dtype=b.dtype, device=dev) + b.sum() * 0
-            r = torch.zeros(N, dtype=torch.int32)
-        r = torch.as_tensor(r).to(device=dev, dtype=torch.int32).contiguous() if r is not None else None
-        return b.contiguous(), r
-    bx_d, rx_d = put(bx, rx)
-    by_d, ry_d = put(by, ry)
-    return fx, on_cpu, lx, bx.shape[1], by.shape[1], bx_d, by_d, rx_d, ry_d
-
-
 def _search(xb, yb, px, py, k, n):
     d2, idx = _KnnPoints.apply(xb, yb, px, py, k)
     return d2[:, :n], idx[:, :n]
@@ -193,17 +110,11 @@ def knn_points(x, y, k=8, x_rows=None, y_rows=None):
     other columns, pad rows and idx = -1 entries get zero, and the choice of neighbours gets none.  The forward and the x-gradient are
     bit-reproducible; the y-gradient sums through float atomics and is not, from run to run.
     """
-    _check_k(k, "knn_points")
-    form, on_cpu, lens, n, _, xb, yb, rx, ry = _inputs(x, y, x_rows, y_rows, "knn_points")
+    _clouds._check_k(k, "knn_points", K_MIN, K_MAX)
+    form, on_cpu, lens, n, _, xb, yb, rx, ry = _clouds.pair(x, y, x_rows, y_rows, "knn_points")
     px, py = _Prepared(xb.detach(), rx), _Prepared(yb.detach(), ry)
-    d2, idx = _search(xb, yb, px, py, k, n)
-    if on_cpu:
-        d2, idx = d2.cpu(), idx.cpu()
-    if form == "list":
-        return [d2[b, :lens[b]] for b in range(len(lens))], [idx[b, :lens[b]] for b in range(len(lens))]
-    if form == "single":
-        return d2[0], idx[0]
-    return d2, idx
+    d2, idx = _KnnPoints.apply(xb, yb, px, py, k)
+    return _clouds.restore(form, on_cpu, n, lens, [(ROW, d2), (ROW, idx)])
 
 
 def _direction(d2, rows, n):
@@ -227,8 +138,8 @@ def chamfer_distance(x, y, x_rows=None, y_rows=None, reduction="mean"):
     as knn_points describes, and through the same float atomics.
     """
     if not isinstance(reduction, str) or reduction not in REDUCTIONS:
-        _err("chamfer_distance: reduction must be one of %s, got %r" % (", ".join(REDUCTIONS), reduction))
-    form, on_cpu, _, n, m, xb, yb, rx, ry = _inputs(x, y, x_rows, y_rows, "chamfer_distance")
+        raise ValueError("chamfer_distance: reduction must be one of %s, got %r" % (", ".join(REDUCTIONS), reduction))
+    form, on_cpu, _, n, m, xb, yb, rx, ry = _clouds.pair(x, y, x_rows, y_rows, "chamfer_distance")
     px, py = _Prepared(xb.detach(), rx), _Prepared(yb.detach(), ry)
     d_xy, _ = _search(xb, yb, px, py, 1, n)
     d_yx, _ = _search(yb, xb, py, px, 1, m)

@@ -13,8 +13,9 @@ import numbers
 
 import torch
 
-from . import _lib
-from ._ops import _DT, _p, _stream, _on, compute_device
+from . import _clouds, _lib
+from ._clouds import ROW, CLOUD, VOXEL
+from ._ops import _DT, _p, _stream, _on, _workspace
 
 _ERR = {1: "a voxel coordinate |floor((p - origin) / voxel_size)| reaches 2^62",
         2: "its voxel coordinates span more than 64 bits (w_x + w_y + w_z > 64)"}
@@ -30,9 +31,7 @@ class _Voxel(torch.autograd.Function):
         dt = _DT[pts.dtype]
         lib = _lib.load()
         ws_bytes = lib.dicp_voxel_workspace_bytes(dt, N, m, c)
-        buf = torch.empty(ws_bytes + 256, dtype=torch.uint8, device=pts.device)
-        shift = (-buf.data_ptr()) % 256
-        ws = buf[shift:]
+        ws = _workspace(ws_bytes, pts.device)
         info = torch.empty(N + 1, dtype=torch.int32, device=pts.device)
         with _on(pts.device):
             st = _stream()
@@ -68,15 +67,6 @@ class _Voxel(torch.autograd.Function):
             _lib.check(_lib.load().dicp_voxel_backward(_DT[g.dtype], _p(g) if M else None, _p(inverse), _p(counts) if M else None, N, m, M, c,
                                                        _p(grad), _stream()), "dicp_voxel_backward")
         return grad, None, None, None, None
-
-
-def _check_points(t, what):
-    if not isinstance(t, torch.Tensor):
-        raise ValueError("voxel_downsample: %s must be a tensor, got %s" % (what, type(t).__name__))
-    if t.dtype not in _DT:
-        raise ValueError("voxel_downsample: %s must be float32 or float64, got %s" % (what, t.dtype))
-    if t.dim() < 1 or t.shape[-1] < 3:
-        raise ValueError("voxel_downsample: %s needs at least 3 columns (x, y, z), got shape %s" % (what, tuple(t.shape)))
 
 
 def _real_values(x, what):
@@ -135,40 +125,9 @@ def voxel_downsample(points, voxel_size, rows=None, origin=None, min_points=1, r
     """
     if isinstance(min_points, bool) or not isinstance(min_points, numbers.Integral) or min_points < 1 or min_points > 2 ** 31 - 1:
         raise ValueError("voxel_downsample: min_points must be an int >= 1, got %r" % (min_points,))
-    is_list = isinstance(points, (list, tuple))
-    if is_list:
-        if not points:
-            raise ValueError("voxel_downsample: empty list")
-        for i, t in enumerate(points):
-            _check_points(t, "points[%d]" % i)
-            if t.dim() != 2:
-                raise ValueError("voxel_downsample: points[%d] must be (m_b, c), got shape %s" % (i, tuple(t.shape)))
-        if len({t.shape[1] for t in points}) != 1 or len({t.dtype for t in points}) != 1 or len({t.device for t in points}) != 1:
-            raise ValueError("voxel_downsample: the clouds of a list need one column count, dtype and device")
-        if rows is not None:
-            raise ValueError("voxel_downsample: rows comes from the list itself")
-        lens = [t.shape[0] for t in points]
-        if max(lens) < 1:
-            raise ValueError("voxel_downsample: every cloud of the list is empty")
-        batch = torch.nn.utils.rnn.pad_sequence(list(points), batch_first=True)
-        rows = torch.tensor(lens, dtype=torch.int32)
-    else:
-        _check_points(points, "points")
-        if points.dim() not in (2, 3):
-            raise ValueError("voxel_downsample: points must be (m, c) or (N, m, c), got shape %s" % (tuple(points.shape),))
-        batch = points if points.dim() == 3 else points.unsqueeze(0)
-    N, m, c = batch.shape
-    if N < 1 or m < 1:
-        raise ValueError("voxel_downsample: empty batch, shape %s" % (tuple(batch.shape),))
+    form, batch, rows, lens = _clouds.check(points, rows, "voxel_downsample", flat_rows=True)
+    N, m = batch.shape[0], batch.shape[1]
     size = _voxel_size(voxel_size, batch.dtype)
-    if rows is not None:
-        r = torch.as_tensor(rows)
-        if r.dtype.is_floating_point or r.dtype.is_complex or r.dtype == torch.bool or r.numel() != N:
-            raise ValueError("voxel_downsample: rows must be %d integer counts" % N)
-        if not r.is_cuda:
-            host = r.reshape(-1)
-            if int(host.min()) < 0 or int(host.max()) > m:
-                raise ValueError("voxel_downsample: rows must lie in [0, %d]" % m)
     o = None
     if origin is not None:
         shape, t = _real_values(origin, "origin")
@@ -178,21 +137,8 @@ def voxel_downsample(points, voxel_size, rows=None, origin=None, min_points=1, r
         if not (bool(torch.isfinite(t).all()) and bool(torch.isfinite(o).all())):
             raise ValueError("voxel_downsample: origin must be finite in %s" % batch.dtype)
 
-    on_cpu = not batch.is_cuda
-    dev = compute_device() if on_cpu else batch.device
-    x = batch.to(dev).contiguous()
-    rows_d = torch.as_tensor(rows).to(device=dev, dtype=torch.int32).reshape(-1).contiguous() if rows is not None else None
-    o_d = o.to(dev).contiguous() if o is not None else None
+    on_cpu, x, rows_d = _clouds.place(batch, rows)
+    o_d = o.to(x.device).contiguous() if o is not None else None
     cent, counts, inverse, rows_out, rows_host = _Voxel.apply(x, rows_d, size, o_d, int(min_points))
-    outs = [cent, rows_out] + ([counts] if return_counts else []) + ([inverse] if return_inverse else [])
-    if on_cpu:
-        outs = [o_.cpu() for o_ in outs]
-    if is_list or points.dim() == 2:
-        per = [int(v) for v in rows_host]
-        n_in = lens if is_list else [m]
-
-        def cloud(b):                                       # centroids / counts: the cloud's voxels; rows_out: 0-d; inverse: the cloud's rows
-            kinds = ["voxels", "count"] + (["voxels"] if return_counts else []) + (["rows"] if return_inverse else [])
-            return [t[b] if k == "count" else t[b, :(per[b] if k == "voxels" else n_in[b])] for k, t in zip(kinds, outs)]
-        outs = [list(col) for col in zip(*[cloud(b) for b in range(N)])] if is_list else cloud(0)
-    return tuple(outs)
+    outs = [(VOXEL, cent), (CLOUD, rows_out)] + ([(VOXEL, counts)] if return_counts else []) + ([(ROW, inverse)] if return_inverse else [])
+    return _clouds.restore(form, on_cpu, m, lens, outs, voxels=rows_host)

@@ -69,7 +69,6 @@ the reference alone; the seeds are chosen so); only the edge sets place some.
 import ctypes
 import math
 import os
-import subprocess
 
 import numpy as np
 import torch
@@ -846,10 +845,6 @@ def reference(ar, cfg, inp, cot=None, allow_ties=False):
 
 
 # ---------------------------------------------------------------- the g++ build of the header (tests/hostcheck), shared by the CPU tests
-_HERE = os.path.dirname(os.path.abspath(__file__))
-HOSTCHECK_SRC = os.path.join(_HERE, "hostcheck", "hostcheck.cpp")
-HOSTCHECK_LIB = os.path.join(_HERE, "hostcheck", "libhostcheck.so")
-MATH_HEADER = os.path.join(_HERE, "..", "dicp_amd", "csrc", "dicp_math.h")
 
 
 class WeightParams(ctypes.Structure):
@@ -858,10 +853,12 @@ class WeightParams(ctypes.Structure):
                 ("loss_delta", ctypes.c_double), ("match_thresh", ctypes.c_double)]
 
 
+HOSTCHECK_SRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostcheck", "hostcheck.cpp")
+
+
 def load_hostcheck():
-    if (not os.path.exists(HOSTCHECK_LIB) or os.path.getmtime(HOSTCHECK_LIB) < max(os.path.getmtime(HOSTCHECK_SRC), os.path.getmtime(MATH_HEADER))):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-Wno-unknown-pragmas", "-o", HOSTCHECK_LIB, HOSTCHECK_SRC])
-    lib = ctypes.CDLL(HOSTCHECK_LIB)
+    import hostbuild
+    lib = hostbuild.build("hostcheck.cpp", "hostcheck")
     assert lib.hc_sizeof_params() == ctypes.sizeof(WeightParams)
     return lib
 

@@ -9,8 +9,6 @@ run before any device work.
 """
 import ctypes
 import os
-import shutil
-import subprocess
 import sys
 
 import numpy as np
@@ -23,19 +21,14 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 import ball_clouds as bc  # noqa: E402
 from ball_ref import ball_ref, same  # noqa: E402
+import hostbuild  # noqa: E402
 
-SRC = os.path.join(HERE, "hostcheck", "ball_check.cpp")
-HAVE_GXX = shutil.which("g++") is not None
 DTYPES = [np.float32, np.float64]
 
 
 @pytest.fixture(scope="module")
-def check(tmp_path_factory):
-    if not HAVE_GXX:
-        pytest.skip("g++ not available")
-    lib_path = str(tmp_path_factory.mktemp("ball_check") / "libball_check.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-Wall", "-Wno-unknown-pragmas", "-o", lib_path, SRC])
-    lib = ctypes.CDLL(lib_path)
+def check():
+    lib = hostbuild.build("ball_check.cpp", "ball_check", ("-Wall",))
     vp, i32 = ctypes.c_void_p, ctypes.c_int
     lib.bc_run_f32.argtypes = [vp, i32, i32, i32, vp, i32, i32, i32, ctypes.c_float, i32, vp, vp, vp, vp]
     lib.bc_run_f64.argtypes = [vp, i32, i32, i32, vp, i32, i32, i32, ctypes.c_double, i32, vp, vp, vp, vp]

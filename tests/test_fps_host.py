@@ -7,8 +7,6 @@ own invariants are checked, and the argument checks of ``sample_farthest_points`
 """
 import ctypes
 import os
-import shutil
-import subprocess
 import sys
 
 import numpy as np
@@ -22,18 +20,13 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 import fps_clouds as fc  # noqa: E402
 from fps_ref import fps_ref  # noqa: E402
+import hostbuild  # noqa: E402
 
-SRC = os.path.join(HERE, "hostcheck", "fps_check.cpp")
-HAVE_GXX = shutil.which("g++") is not None
 
 
 @pytest.fixture(scope="module")
-def check(tmp_path_factory):
-    if not HAVE_GXX:
-        pytest.skip("g++ not available")
-    lib_path = str(tmp_path_factory.mktemp("fps_check") / "libfps_check.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-Wall", "-Wno-unknown-pragmas", "-o", lib_path, SRC])
-    lib = ctypes.CDLL(lib_path)
+def check():
+    lib = hostbuild.build("fps_check.cpp", "fps_check", ("-Wall",))
     vp, i32 = ctypes.c_void_p, ctypes.c_int
     for fn in (lib.fc_run_f32, lib.fc_run_f64):
         fn.argtypes = [vp, i32, i32, ctypes.c_longlong, i32, i32, vp, vp]

@@ -6,8 +6,7 @@ on inputs that are hard for a walk over one sorted axis; the argument checks of 
 """
 import ctypes
 import os
-import shutil
-import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -15,18 +14,13 @@ import torch
 
 from dicp_amd.knn import chamfer_distance, knn_points
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "hostcheck", "knn_check.cpp")
-HAVE_GXX = shutil.which("g++") is not None
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import hostbuild  # noqa: E402
 
 
 @pytest.fixture(scope="module")
-def kc(tmp_path_factory):
-    if not HAVE_GXX:
-        pytest.skip("g++ not available")
-    lib_path = str(tmp_path_factory.mktemp("knn_check") / "libknn_check.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-Wno-unknown-pragmas", "-o", lib_path, SRC])
-    lib = ctypes.CDLL(lib_path)
+def kc():
+    lib = hostbuild.build("knn_check.cpp", "knn_check")
     vp, i32 = ctypes.c_void_p, ctypes.c_int
     for name in ("kc_knn_f32", "kc_knn_f64"):
         fn = getattr(lib, name)

@@ -6,8 +6,7 @@ tests/hostcheck/normals_check.cpp and held to numpy's eigh (forward) and to torc
 """
 import ctypes
 import os
-import shutil
-import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -15,18 +14,13 @@ import torch
 
 from dicp_amd.normals import estimate_normals
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "hostcheck", "normals_check.cpp")
-HAVE_GXX = shutil.which("g++") is not None
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import hostbuild  # noqa: E402
 
 
 @pytest.fixture(scope="module")
-def nc(tmp_path_factory):
-    if not HAVE_GXX:
-        pytest.skip("g++ not available")
-    lib_path = str(tmp_path_factory.mktemp("normals_check") / "libnormals_check.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-Wno-unknown-pragmas", "-o", lib_path, SRC])
-    lib = ctypes.CDLL(lib_path)
+def nc():
+    lib = hostbuild.build("normals_check.cpp", "normals_check")
     vp, i32, f64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_double
     lib.nc_forward.argtypes = [vp, i32, vp, vp, vp, vp, vp]
     lib.nc_forward.restype = None

@@ -68,12 +68,8 @@ def _has_fma():
 @pytest.fixture(scope="module")
 def host_contracted():
     """the same header with a * b + c contracted into one rounding, as the device build does (-ffp-contract=on there): other roundings, same model"""
-    import ctypes
-    import subprocess
-    lib = os.path.join(HERE, "hostcheck", "libhostcheck_fma.so")
-    if not os.path.exists(lib) or os.path.getmtime(lib) < max(os.path.getmtime(R.HOSTCHECK_SRC), os.path.getmtime(R.MATH_HEADER)):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-mfma", "-ffp-contract=fast", "-Wno-unknown-pragmas", "-o", lib, R.HOSTCHECK_SRC])
-    return R.HostBackend(ctypes.CDLL(lib))
+    import hostbuild
+    return R.HostBackend(hostbuild.build("hostcheck.cpp", "hostcheck_fma", ("-mfma", "-ffp-contract=fast")))
 
 
 @pytest.mark.skipif(not _has_fma(), reason="this CPU has no fused multiply-add")

@@ -6,8 +6,7 @@ tests/hostcheck/voxel_check.cpp and held to numpy: coordinates floor((p - o) / s
 """
 import ctypes
 import os
-import shutil
-import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -15,18 +14,13 @@ import torch
 
 from dicp_amd.voxel import voxel_downsample
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "hostcheck", "voxel_check.cpp")
-HAVE_GXX = shutil.which("g++") is not None
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import hostbuild  # noqa: E402
 
 
 @pytest.fixture(scope="module")
-def vc(tmp_path_factory):
-    if not HAVE_GXX:
-        pytest.skip("g++ not available")
-    lib_path = str(tmp_path_factory.mktemp("voxel_check") / "libvoxel_check.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-Wno-unknown-pragmas", "-o", lib_path, SRC])
-    lib = ctypes.CDLL(lib_path)
+def vc():
+    lib = hostbuild.build("voxel_check.cpp", "voxel_check")
     vp, i32, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
     lib.vc_coord_f32.argtypes = [vp, i32, ctypes.c_float, ctypes.c_float, vp, vp]
     lib.vc_coord_f64.argtypes = [vp, i32, ctypes.c_double, ctypes.c_double, vp, vp]
