@@ -26,6 +26,20 @@ class CellGrid:
     """
 
     def __init__(self, pts, rows, radius):
+        self._build(pts, rows, lambda lib, dt, N, m, c: lib.dicp_ball_grid_build(
+            dt, _p(pts), c, _p(rows), N, m, _p(radius), None, _p(self.plans), _p(self.keys), _p(self.perm), _p(self.rows4), _stream()),
+            "dicp_ball_grid_build")
+
+    @classmethod
+    def by_density(cls, pts, rows):
+        """The grid without a radius (dicp_knn_grid_build), for the k-NN search: the cell edge is chosen per cloud on the device from the
+        number and the bounds of its live rows, about two rows per cell of the bounding box (csrc/dicp_gridknn.h)."""
+        self = cls.__new__(cls)
+        self._build(pts, rows, lambda lib, dt, N, m, c: lib.dicp_knn_grid_build(
+            dt, _p(pts), c, _p(rows), N, m, _p(self.plans), _p(self.keys), _p(self.perm), _p(self.rows4), _stream()), "dicp_knn_grid_build")
+        return self
+
+    def _build(self, pts, rows, call, what):
         N, m, c = pts.shape
         lib = _lib.load()
         dev = pts.device
@@ -36,8 +50,7 @@ class CellGrid:
         self.perm = torch.empty((N, P), dtype=torch.int32, device=dev)
         self.rows4 = torch.empty((N, P, 4), dtype=pts.dtype, device=dev)
         with _on(dev):
-            _lib.check(lib.dicp_ball_grid_build(_DT[pts.dtype], _p(pts), c, _p(rows), N, m, _p(radius), None, _p(self.plans), _p(self.keys),
-                                                _p(self.perm), _p(self.rows4), _stream()), "dicp_ball_grid_build")
+            _lib.check(call(lib, _DT[pts.dtype], N, m, c), what)
 
     def order(self, x, x_rows):
         """-> (keys (N,Pn) int64, perm (N,Pn) int32): the rows of x (N,n,c) in the order of this grid's cells"""
@@ -78,21 +91,61 @@ class _BallQuery(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_d2, _g_idx, _g_counts):
-        nothing = (None,) * 7
-        want_x, want_y = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        if g_d2 is None or not (want_x or want_y):
-            return nothing
-        x, = ctx.saved_tensors
-        N, n, cx, m, cy = ctx.shape
-        grid = ctx.grid
-        dtype, dev = g_d2.dtype, g_d2.device
-        gx = torch.empty((N, n, cx), dtype=dtype, device=dev) if want_x else None
-        gy = torch.empty((N, m, cy), dtype=dtype, device=dev) if want_y else None
-        g_d2 = g_d2.contiguous()
+        return _backward(ctx, g_d2, 7)
+
+
+def _backward(ctx, g_d2, n_inputs):
+    """dicp_ball_query_backward from what a forward on a CellGrid saved: the gradients of x and y, None for the other inputs"""
+    nothing = (None,) * n_inputs
+    want_x, want_y = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+    if g_d2 is None or not (want_x or want_y):
+        return nothing
+    x, = ctx.saved_tensors
+    N, n, cx, m, cy = ctx.shape
+    grid = ctx.grid
+    dtype, dev = g_d2.dtype, g_d2.device
+    gx = torch.empty((N, n, cx), dtype=dtype, device=dev) if want_x else None
+    gy = torch.empty((N, m, cy), dtype=dtype, device=dev) if want_y else None
+    g_d2 = g_d2.contiguous()
+    with _on(dev):
+        _lib.check(_lib.load().dicp_ball_query_backward(_DT[dtype], _p(g_d2), _p(x), cx, n, _p(grid.rows4), _p(grid.perm), m, cy, N, ctx.k,
+                                                        _p(ctx.ws), _p(gx), _p(gy), _stream()), "dicp_ball_query_backward")
+    return (gx, gy) + nothing[2:]
+
+
+class _GridKnn(torch.autograd.Function):
+    """(x (N,n,c), y (N,m,c)) -> (d2 (N,n,k), idx (N,n,k) int64): the k nearest rows on y's density grid (dicp_knn_grid_query); the
+    backward is ball_query's."""
+
+    @staticmethod
+    def forward(ctx, x, y, grid, xkeys, xperm, k, visited, passes):
+        N, n, cx = x.shape
+        m, cy = y.shape[1], y.shape[2]
+        dt = _DT[x.dtype]
+        lib = _lib.load()
+        dev = x.device
+        ws_bytes = lib.dicp_ball_query_workspace_bytes(dt, N, n, k)
+        d2 = torch.empty((N, n, k), dtype=x.dtype, device=dev)
+        idx = torch.empty((N, n, k), dtype=torch.int64, device=dev)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         with _on(dev):
-            _lib.check(_lib.load().dicp_ball_query_backward(_DT[dtype], _p(g_d2), _p(x), cx, n, _p(grid.rows4), _p(grid.perm), m, cy, N, ctx.k,
-                                                            _p(ctx.ws), _p(gx), _p(gy), _stream()), "dicp_ball_query_backward")
-        return (gx, gy) + nothing[2:]
+            _lib.check(lib.dicp_knn_grid_query(dt, _p(x), cx, n, _p(xkeys), _p(xperm), _p(grid.plans), _p(grid.keys), _p(grid.perm), _p(grid.rows4),
+                                               m, N, k, _p(d2), _p(idx), _p(ws), ws_bytes, _p(visited), _p(passes), _stream()), "dicp_knn_grid_query")
+        ctx.save_for_backward(x)
+        ctx.grid, ctx.ws, ctx.k, ctx.shape = grid, ws, k, (N, n, cx, m, cy)
+        ctx.mark_non_differentiable(idx)
+        ctx.set_materialize_grads(False)
+        return d2, idx
+
+    @staticmethod
+    def backward(ctx, g_d2, _g_idx):
+        return _backward(ctx, g_d2, 8)
+
+
+def grid_knn(xb, yb, rx, grid, k, visited=None, passes=None):
+    """The k nearest rows of yb (N,m,c), whose density grid is `grid`, for every row of xb (N,n,c) -> (d2, idx) (N,n,k)"""
+    xkeys, xperm = grid.order(xb.detach(), rx)
+    return _GridKnn.apply(xb, yb, grid, xkeys, xperm, k, visited, passes)
 
 
 def _err(msg):

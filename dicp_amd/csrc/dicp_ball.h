@@ -159,13 +159,14 @@ DICP_HD uint64_t ball_point_key(const BallPlan<T>& P, T x, T y, T z) {
     return ball_key(P, c[0], c[1], c[2]);
 }
 
-// The cells cell(fl(p_d - R)) .. cell(fl(p_d + R)) intersected with 0 .. hi_d; false when the intersection is empty on some axis
+// The cells cell(fl(p_d - R)) .. cell(fl(p_d + R)) intersected with 0 .. hi_d; false when the intersection is empty on some axis.
+// ball_range_at takes the half-width as an argument (dicp_gridknn.h searches one grid at several), ball_range the plan's own.
 template <typename T>
-DICP_HD bool ball_range(const BallPlan<T>& P, T x, T y, T z, int64_t* lo, int64_t* hi) {
+DICP_HD bool ball_range_at(const BallPlan<T>& P, T R, T x, T y, T z, int64_t* lo, int64_t* hi) {
     const T p[3] = {x, y, z};
     for (int d = 0; d < 3; ++d) {
-        const T a = p[d] - P.R;
-        const T b = p[d] + P.R;
+        const T a = p[d] - R;
+        const T b = p[d] + R;
         if (!ball_cell(a, P.o[d], P.s[d], &lo[d]) || !ball_cell(b, P.o[d], P.s[d], &hi[d])) return false;
         if (lo[d] < 0) lo[d] = 0;
         if (hi[d] > P.hi[d]) hi[d] = P.hi[d];
@@ -173,6 +174,9 @@ DICP_HD bool ball_range(const BallPlan<T>& P, T x, T y, T z, int64_t* lo, int64_
     }
     return true;
 }
+
+template <typename T>
+DICP_HD bool ball_range(const BallPlan<T>& P, T x, T y, T z, int64_t* lo, int64_t* hi) { return ball_range_at(P, P.R, x, y, z, lo, hi); }
 
 // The first of keys[0, n) (ascending) that is not below k; n when there is none
 template <typename Keys>

@@ -15,6 +15,12 @@ from ._ops import _DT, _p, _stream, _on
 
 K_MIN, K_MAX = 1, 32
 REDUCTIONS = ("mean", "sum", "none")
+METHODS = ("walk", "grid")
+
+
+def _check_method(method, what):
+    if not isinstance(method, str) or method not in METHODS:
+        raise ValueError('%s: method must be "walk" or "grid", got %r' % (what, method))
 
 
 class _Prepared:
@@ -91,7 +97,7 @@ def _search(xb, yb, px, py, k, n):
     return d2[:, :n], idx[:, :n]
 
 
-def knn_points(x, y, k=8, x_rows=None, y_rows=None):
+def knn_points(x, y, k=8, x_rows=None, y_rows=None, method="walk", _visited=None, _passes=None):
     """The k nearest rows of y for every row of x, exactly, with gradients of the squared distances.
 
     x, y: one cloud each (n, c) and (m, c); a padded batch each (N, n, c) and (N, m, c) with optional integer row counts x_rows / y_rows (N,);
@@ -99,6 +105,10 @@ def knn_points(x, y, k=8, x_rows=None, y_rows=None):
         can be passed as they are).  CPU tensors are computed on the GPU and returned on the CPU.  Row counts are checked on the host only
         when they are CPU tensors.
     k: an int in [1, 32].
+    method: "walk" (the default) searches along the x-sorted cloud; "grid" sorts y into a cell grid whose cell edge is chosen on the device
+        from y's own density (ball.CellGrid.by_density, about two rows per cell) and lets every query grow a box of cells until its k-th
+        distance is proved final (dicp_knn_grid_build / dicp_knn_grid_query; the proof is csrc/dicp_gridknn.h).  Both are exact and return
+        the same bits; they differ in speed only (README, "Nearest neighbours and Chamfer distance").
 
     Definition: d2(i, j) = (xx + yy) + zz with dx = y_j.x - x_i.x, xx = dx * dx (and so on), in the inputs' dtype, as separate roundings.  The
     candidates of query i of cloud b are the rows j < y_rows[b] whose d2 is finite; the result is the first k_eff = min(k, #candidates) of
@@ -108,12 +118,18 @@ def knn_points(x, y, k=8, x_rows=None, y_rows=None):
 
     Gradients flow from d2 to x[..., :3] (sum_j 2 g_ij (x_i - y_idx)) and y[..., :3] (-sum 2 g_ij (x_i - y_l) over the entries with idx = l);
     other columns, pad rows and idx = -1 entries get zero, and the choice of neighbours gets none.  The forward and the x-gradient are
-    bit-reproducible; the y-gradient sums through float atomics and is not, from run to run.
+    bit-reproducible; the y-gradient sums through float atomics and is not, from run to run.  With method="grid" the backward is
+    ball_query's (dicp_ball_query_backward), with the same properties.
     """
     _clouds._check_k(k, "knn_points", K_MIN, K_MAX)
+    _check_method(method, "knn_points")
     form, on_cpu, lens, n, _, xb, yb, rx, ry = _clouds.pair(x, y, x_rows, y_rows, "knn_points")
-    px, py = _Prepared(xb.detach(), rx), _Prepared(yb.detach(), ry)
-    d2, idx = _KnnPoints.apply(xb, yb, px, py, k)
+    if method == "grid":
+        from .ball import CellGrid, grid_knn                # (ball.py imports this module)
+        d2, idx = grid_knn(xb, yb, rx, CellGrid.by_density(yb.detach(), ry), k, _visited, _passes)
+    else:
+        px, py = _Prepared(xb.detach(), rx), _Prepared(yb.detach(), ry)
+        d2, idx = _KnnPoints.apply(xb, yb, px, py, k)
     return _clouds.restore(form, on_cpu, n, lens, [(ROW, d2), (ROW, idx)])
 
 
@@ -127,7 +143,7 @@ def _direction(d2, rows, n):
     return s / cnt.clamp(min=1).to(d2.dtype)
 
 
-def chamfer_distance(x, y, x_rows=None, y_rows=None, reduction="mean"):
+def chamfer_distance(x, y, x_rows=None, y_rows=None, reduction="mean", method="walk"):
     """Chamfer distance between two clouds: for cloud b, mean_{i < n_b} d2(x_i, NN_y(x_i)) + mean_{j < m_b} d2(y_j, NN_x(y_j)).
 
     x, y and the row counts: as knn_points.  d2 as knn_points defines it (squared, in the inputs' dtype).  A direction whose query side is
@@ -136,13 +152,20 @@ def chamfer_distance(x, y, x_rows=None, y_rows=None, reduction="mean"):
 
     Each cloud is sorted once and searched in both directions (two k = 1 searches of knn_points); gradients flow to x[..., :3] and y[..., :3]
     as knn_points describes, and through the same float atomics.
+    method: as knn_points.  "grid" builds the cell grid of each cloud once and searches each direction on the other cloud's grid.
     """
     if not isinstance(reduction, str) or reduction not in REDUCTIONS:
         raise ValueError("chamfer_distance: reduction must be one of %s, got %r" % (", ".join(REDUCTIONS), reduction))
+    _check_method(method, "chamfer_distance")
     form, on_cpu, _, n, m, xb, yb, rx, ry = _clouds.pair(x, y, x_rows, y_rows, "chamfer_distance")
-    px, py = _Prepared(xb.detach(), rx), _Prepared(yb.detach(), ry)
-    d_xy, _ = _search(xb, yb, px, py, 1, n)
-    d_yx, _ = _search(yb, xb, py, px, 1, m)
+    if method == "grid":
+        from .ball import CellGrid, grid_knn
+        gx, gy = CellGrid.by_density(xb.detach(), rx), CellGrid.by_density(yb.detach(), ry)
+        d_xy, d_yx = grid_knn(xb, yb, rx, gy, 1)[0][:, :n], grid_knn(yb, xb, ry, gx, 1)[0][:, :m]
+    else:
+        px, py = _Prepared(xb.detach(), rx), _Prepared(yb.detach(), ry)
+        d_xy, _ = _search(xb, yb, px, py, 1, n)
+        d_yx, _ = _search(yb, xb, py, px, 1, m)
     per = _direction(d_xy, rx, n) + _direction(d_yx, ry, m)
     out = per if reduction == "none" else (per.mean() if reduction == "mean" else per.sum())
     return out.cpu() if on_cpu else out

@@ -930,6 +930,25 @@ int dicp_ball_query(int dtype, const void* x, int cx, int n, const uint64_t* x_k
 int dicp_ball_query_backward(int dtype, const void* g_d2, const void* x, int cx, int n, const void* y_rows4, const int32_t* y_perm, int m, int cy,
                              int N, int k, const void* fwd_workspace, void* grad_x, void* grad_y, void* stream);
 
+/* Exact k nearest neighbours on the same cell grid, without a radius (dicp_amd/knn.py: knn_points / chamfer_distance with method="grid";
+ * the plan, the stopping rule and their proof: csrc/dicp_gridknn.h).  Results as dicp_knn_points defines them: the candidates of a query
+ * are the rows j < rows[b] with three finite coordinates and a finite d2, the list their first min(k, #candidates) in (d2, index) order.
+ * dicp_knn_grid_build: the grid of every cloud as dicp_ball_grid_build(order_by = NULL) lays it out (plans, keys, perm, rows4: same
+ *   sizes, dicp_ball_grid_slots / dicp_ball_plan_bytes), the cell edge chosen per cloud on the device from the live rows' number and
+ *   bounds (about two rows per cell of the bounding box; walls, lines and single points included) instead of a radius.  O(m) memory, no
+ *   host read-back.  The queries of such a grid are ordered by dicp_ball_grid_build(order_by = its plans), unchanged.
+ * dicp_knn_grid_query: x (N,n,cx) T the queries, x_keys / x_perm their order, the grid of y.  d2 (N,n,k) T, idx (N,n,k) int64, +inf / -1
+ *   beyond the candidates and for query rows past x_rows[b] or with a non-finite coordinate, in the original query order.  Every query
+ *   grows its box of cells until its k-th d2 is proved final.  workspace: dicp_ball_query_workspace_bytes(dtype, N, n, k) bytes, laid
+ *   out as dicp_ball_query's, so that the backward is dicp_ball_query_backward.  visited / passes: optional (N) rows scanned and boxes
+ *   computed per cloud (diagnostics).  No float atomics: bit-reproducible.  Nothing is read back; every launch is capturable. */
+int dicp_knn_grid_build(int dtype, const void* pts, int c, const int32_t* rows, int N, int m, void* plans, uint64_t* keys, int32_t* perm,
+                        void* rows4, void* stream);
+int dicp_knn_grid_query(int dtype, const void* x, int cx, int n, const uint64_t* x_keys, const int32_t* x_perm, const void* y_plans,
+                        const uint64_t* y_keys, const int32_t* y_perm, const void* y_rows4, int m, int N, int k,
+                        void* d2, int64_t* idx, void* workspace, size_t workspace_bytes, unsigned long long* visited, unsigned long long* passes,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif
