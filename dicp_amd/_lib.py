@@ -242,6 +242,9 @@ _SIGNATURES = {
     "dicp_normals_workspace_bytes": ([i32, i32, i32, i32, i32, i32], ctypes.c_size_t),
     "dicp_normals_forward": ([i32, vp, i32, vp, i32, i32, i32, vp, i32, vp, vp, vp, vp, ctypes.c_size_t, vp, vp], ctypes.c_int),
     "dicp_normals_backward": ([i32, vp, vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, ctypes.c_size_t, vp], ctypes.c_int),
+    "dicp_normals_grid_workspace_bytes": ([i32, i32, i32, i32, i32, i32], ctypes.c_size_t),
+    "dicp_normals_grid_forward": ([i32, vp, i32, vp, i32, i32, i32, vp, i32, vp, vp, vp, vp, ctypes.c_size_t, vp, vp, vp], ctypes.c_int),
+    "dicp_normals_grid_backward": ([i32, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, ctypes.c_size_t, vp], ctypes.c_int),
     "dicp_voxel_workspace_bytes": ([i32, i32, i32, i32], ctypes.c_size_t),
     "dicp_voxel_count": ([i32, vp, i32, vp, i32, i32, f64, f64, f64, vp, i32, i32, vp, vp, ctypes.c_size_t, vp], ctypes.c_int),
     "dicp_voxel_reduce": ([i32, vp, i32, i32, i32, i32, vp, ctypes.c_size_t, vp, vp, vp, vp], ctypes.c_int),

@@ -1,6 +1,8 @@
 // The device structure of a cloud's cell grid, shared by csrc/ball_query.hip (fixed-radius neighbours) and csrc/knn_grid.hip (k nearest
 // neighbours): the bounds of a cloud's live rows for the plan kernels, the keys, the bitonic sort of (key, row) pairs and the pack of the
-// sorted rows.  What the stages are for is told at the top of ball_query.hip; the arithmetic is csrc/dicp_ball.h.
+// sorted rows; and the whole build of a density grid (the plan of csrc/dicp_gridknn.h, then those stages), shared by csrc/knn_grid.hip and
+// csrc/normals.hip (estimate_normals with method="grid").  What the stages are for is told at the top of ball_query.hip; the arithmetic
+// is csrc/dicp_ball.h.
 // Everything here has internal linkage (anonymous namespace): each .hip file gets its own copy.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -8,6 +10,7 @@
 
 #include "dicp_common.h"
 #include "dicp_ball.h"
+#include "dicp_gridknn.h"
 
 namespace {
 
@@ -173,6 +176,22 @@ int ball_grid_stages(const T* pts, int c, const int32_t* rows, int N, int m, con
     if (rc) return rc;
     if (own) ball_pack_kernel<T><<<grid_1d(total), BLOCK, 0, st>>>(pts, c, N, m, P, pl, perm, (typename V4<T>::type*)rows4);
     return 0;
+}
+
+// The density plan of every cloud (gknn_plan: the cell edge from the number and the bounds of the live rows), one workgroup per cloud
+template <typename T>
+__global__ __launch_bounds__(BLOCK) void gknn_plan_kernel(const T* __restrict__ pts, int c, const int32_t* __restrict__ rows, int m, void* __restrict__ plans) {
+    T mn[3], mx[3];
+    int cnt;
+    ball_cloud_bounds<T>(pts, c, rows, m, mn, mx, cnt);
+    if (threadIdx.x == 0) *(BallPlan<T>*)((char*)plans + (size_t)blockIdx.x * BALL_PLAN_BYTES) = gknn_plan<T>(mn, mx, cnt);
+}
+
+// The density grid of every cloud: plan, keys, sort, pack (the caller brackets it with begin_launch / launch_status)
+template <typename T>
+int gknn_grid_build(const T* pts, int c, const int32_t* rows, int N, int m, void* plans, uint64_t* keys, int32_t* perm, void* rows4, hipStream_t st) {
+    gknn_plan_kernel<T><<<N, BLOCK, 0, st>>>(pts, c, rows, m, plans);
+    return ball_grid_stages<T>(pts, c, rows, N, m, plans, 1, keys, perm, rows4, st);
 }
 
 }  // namespace

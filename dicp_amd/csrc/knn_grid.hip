@@ -2,7 +2,7 @@
 // stopping rule with its proof and the per-query scan are csrc/dicp_gridknn.h; this file is the device structure around them.
 //
 // The grid of a cloud (dicp_knn_grid_build) is ball_query's (csrc/kernels_grid.h: keys, bitonic sort, pack), with one difference: the
-// plan kernel takes the cell edge from the cloud's own density (gknn_plan) instead of a radius.  The layout of plans / keys / perm /
+// plan kernel takes the cell edge from the cloud's own density (gknn_plan) instead of a radius (gknn_grid_build, kernels_grid.h).  The layout of plans / keys / perm /
 // rows4 is dicp_ball_grid_build's, so the queries are ordered by dicp_ball_grid_build(order_by = these plans) and the backward is
 // dicp_ball_query_backward, both unchanged.
 // Search (dicp_knn_grid_query), one lane per sorted query slot: gknn_scan with the keys, rows and permutation read from global memory
@@ -18,14 +18,6 @@
 #include "kernels_grid.h"
 
 namespace {
-
-template <typename T>
-__global__ __launch_bounds__(BLOCK) void gknn_plan_kernel(const T* __restrict__ pts, int c, const int32_t* __restrict__ rows, int m, void* __restrict__ plans) {
-    T mn[3], mx[3];
-    int cnt;
-    ball_cloud_bounds<T>(pts, c, rows, m, mn, mx, cnt);
-    if (threadIdx.x == 0) *(BallPlan<T>*)((char*)plans + (size_t)blockIdx.x * BALL_PLAN_BYTES) = gknn_plan<T>(mn, mx, cnt);
-}
 
 template <typename T, int K>
 __global__ __launch_bounds__(BLOCK) void gknn_query_kernel(const T* __restrict__ x, int cx, int n, int Pn, const uint64_t* __restrict__ xkeys,
@@ -88,12 +80,9 @@ int dicp_knn_grid_build(int dtype, const void* pts, int c, const int32_t* rows, 
         (uintptr_t)rows4 % (4 * ts)) return DICP_ERR_ALIGN;
     hipStream_t st = (hipStream_t)stream;
     begin_launch();
-#define DICP_GKNN_BUILD(T) do { \
-        gknn_plan_kernel<T><<<N, BLOCK, 0, st>>>((const T*)pts, c, rows, m, plans); \
-        if ((rc = ball_grid_stages<T>((const T*)pts, c, rows, N, m, plans, 1, keys, perm, rows4, st))) return rc; \
-    } while (0)
-    if (dtype == DICP_F32) DICP_GKNN_BUILD(float); else DICP_GKNN_BUILD(double);
-#undef DICP_GKNN_BUILD
+    rc = dtype == DICP_F32 ? gknn_grid_build<float>((const float*)pts, c, rows, N, m, plans, keys, perm, rows4, st)
+                           : gknn_grid_build<double>((const double*)pts, c, rows, N, m, plans, keys, perm, rows4, st);
+    if (rc) return rc;
     return launch_status();
 }
 

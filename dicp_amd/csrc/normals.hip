@@ -15,6 +15,18 @@
 // (2/k_eff) G (q_j - mu) to each neighbour j: into an LDS window of the block's slots +- BWD_HALO rows with LDS atomics, outside
 // it into the sorted gradient rows with global atomics; the window is then flushed as contiguous rows, and one
 // dicp_permute_add_rows returns the rows to the original order.  Float atomics: not bit-reproducible from run to run.
+//
+// method="grid" (dicp_normals_grid_forward / dicp_normals_grid_backward) replaces pack, sort and walk; the fit and the backward are the
+// same two kernels on another layout (template parameter GRID):
+//   grid     the density grid of the cloud itself (gknn_grid_build, kernels_grid.h) straight from the (N,m,c) rows: plans, keys, perm,
+//            rows4, P = ball_slots(m) slots per cloud.  The live rows (j < rows[b], three finite coordinates) are slots 0 .. cnt - 1 in
+//            (cell key, index) order, the other rows of the cloud slots cnt .. m - 1 in index order.
+//   search   one lane per slot: gknn_scan (csrc/dicp_gridknn.h) of the slot's own row over the grid, the list of the walk.  The list is
+//            the first k_eff(i) = min(k, #rows with a finite d2 to i) rows in (d2, index) order -- on a cloud the walk defines (live rows
+//            finite, no d2 overflow) the walk's list, entry for entry, so the fit, which sums in list order in double, returns its bits.
+//   layout   row stride P instead of m_pad, rows4 / perm for tgs4 / tperm, live = s < the plan's cnt instead of s < rows[b], and
+//            k_eff = the filled entries of the slot's list instead of min(k, rows[b]).
+// The backward window is BLOCK + 2 * BwdHalo slots of the grid's order, (vx, vy, vz) cell-major.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -22,6 +34,7 @@
 #include "dicp_fill.h"
 #include "dicp_normals.h"
 #include "dicp_topk.h"
+#include "kernels_grid.h"
 
 namespace {
 
@@ -52,6 +65,23 @@ inline NrmLayout nrm_layout(int dtype, int N, int m, int k) {
     L.nbr_s = off;   off = up256(off + (size_t)N * m_pad * k * 4);
     L.scratch_bytes = dicp_sweep_sort_scratch_bytes(dtype, N, (int)m_pad);
     L.scratch = off; off = up256(off + L.scratch_bytes);
+    L.total = off;
+    return L;
+}
+
+// The forward workspace of method="grid" (each part 256-byte aligned); the backward reads plans / perm / rows4 / nbr_s of it
+struct NrmGridLayout {
+    size_t plans, keys, perm, rows4, nbr_s, total;
+};
+inline NrmGridLayout nrm_grid_layout(int dtype, int N, int m, int k) {
+    NrmGridLayout L;
+    const size_t ts = dtype == DICP_F32 ? 4 : 8, P = (size_t)ball_slots(m);
+    size_t off = 0;
+    L.plans = off;   off = up256(off + (size_t)N * BALL_PLAN_BYTES);
+    L.keys = off;    off = up256(off + (size_t)N * P * 8);
+    L.perm = off;    off = up256(off + (size_t)N * P * 4);
+    L.rows4 = off;   off = up256(off + (size_t)N * P * 4 * ts);
+    L.nbr_s = off;   off = up256(off + (size_t)N * P * k * 4);
     L.total = off;
     return L;
 }
@@ -111,6 +141,71 @@ __global__ __launch_bounds__(BLOCK) void normals_knn_kernel(const typename V4<T>
     if (walked) wave_add(walked + b, steps);          // diagnostics: rows walked, one atomic per wave
 }
 
+// ------------------------------------------------------------------ grid search (the scan and its proof: csrc/dicp_gridknn.h)
+// One lane per sorted slot s < m of the cloud's own grid: the query is the slot's row, so the grid's order is the query order and the
+// lanes of a wave sit in the same or adjacent cells (their key searches and row reads hit the same lines).  Slots cnt .. m - 1 hold the
+// rows that take no part (pad rows, non-finite rows): -1 neighbours at their original row.
+template <typename T, int K>
+__global__ __launch_bounds__(BLOCK) void normals_grid_knn_kernel(const void* __restrict__ plans, const uint64_t* __restrict__ keys,
+                                                                 const int32_t* __restrict__ perm, const typename V4<T>::type* __restrict__ rows4,
+                                                                 int N, int m, int P, int k, int bpc, int32_t* __restrict__ nbr_s,
+                                                                 int64_t* __restrict__ nbr_out, unsigned long long* __restrict__ visited,
+                                                                 unsigned long long* __restrict__ passes) {
+    using T4 = typename V4<T>::type;
+    int b, blk;
+    if (!decode_block(bpc, N, b, blk)) return;
+    const int s = blk * BLOCK + threadIdx.x;
+    unsigned long long steps = 0, boxes = 0;
+    if (s < m) {
+        const size_t base = (size_t)b * P;
+        const int orow = min(max(perm[base + s], 0), m - 1);
+        if (s < plan_of<T>(plans, b).cnt) {
+            const BallPlan<T> pl = plan_of<T>(plans, b);
+            const uint64_t* kb = keys + base;
+            auto key = [&](int j) -> uint64_t { return kb[j]; };
+            auto row = [&](int j) -> T4 { return rows4[base + j]; };
+            auto orig = [&](int j) -> int { return perm[base + j]; };
+            T d[K];
+            int id[K], sl[K];
+            topk_init(d, id, sl, k);
+            const auto ins = topk_inserter(d, id, sl, orig);
+            const T4 p = rows4[base + s];
+            const GknnScan r = gknn_scan<T>(pl, d, p, key, row, ins);
+            steps = r.visited;
+            boxes = (unsigned long long)r.passes;
+            const size_t q = base + s;
+#pragma unroll
+            for (int i = 0; i < K; ++i) {
+                if (i < K - k) continue;
+                const int o = i - (K - k);
+                nbr_s[q * k + o] = sl[i];
+                if (nbr_out) nbr_out[((size_t)b * m + orow) * k + o] = id[i];
+            }
+        } else if (nbr_out) {
+            for (int o = 0; o < k; ++o) nbr_out[((size_t)b * m + orow) * k + o] = -1;
+        }
+    }
+    if (visited) wave_add(visited + b, steps);        // diagnostics: rows fed and boxes computed, one atomic per wave each
+    if (passes) wave_add(passes + b, boxes);
+}
+
+// ------------------------------------------------------------------ the two layouts of the fit and the backward
+// GRID = false: the x-sorted cloud (row stride m_pad, tgs4 / tperm, live = s < rows[b], every list k_eff = min(k, rows[b]) long);
+// GRID = true: the cell grid (row stride P, rows4 / perm, live = s < the plan's cnt, a list as long as its filled entries)
+template <typename T, bool GRID>
+__device__ __forceinline__ int nrm_live_rows(const int32_t* __restrict__ rows, const void* __restrict__ plans, int b, int m) {
+    if constexpr (GRID) return min(plan_of<T>(plans, b).cnt, m);
+    else return rows_of(rows, b, m);
+}
+template <bool GRID>
+__device__ __forceinline__ int nrm_k_eff(const int32_t* __restrict__ nb, int k, int mb) {
+    if constexpr (GRID) {
+        int n = 0;
+        for (int o = 0; o < k; ++o) n += nb[o] >= 0;    // (the filled entries lead the list)
+        return n;
+    } else return min(k, mb);
+}
+
 // ------------------------------------------------------------------ per-point eigen-system (forward and backward)
 struct NrmPoint {
     double mu[3], lam[3], v[9], s;
@@ -122,13 +217,13 @@ __device__ __forceinline__ void nrm_point(const typename V4<T>::type* __restrict
     P.k_eff = k_eff;
     double sum[3] = {0.0, 0.0, 0.0};
     for (int o = 0; o < k_eff; ++o) {
-        const auto y = rows4[max(nb[o], 0)];      // (-1 only next to rows whose d2 overflows: output unspecified there)
+        const auto y = rows4[max(nb[o], 0)];      // (-1 only in the walk's lists, next to rows whose d2 overflows: output unspecified there)
         sum[0] += (double)y.x - (double)p.x; sum[1] += (double)y.y - (double)p.y; sum[2] += (double)y.z - (double)p.z;
     }
     P.mu[0] = sum[0] / k_eff; P.mu[1] = sum[1] / k_eff; P.mu[2] = sum[2] / k_eff;
     double C6[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     for (int o = 0; o < k_eff; ++o) {
-        const auto y = rows4[max(nb[o], 0)];      // (-1 only next to rows whose d2 overflows: output unspecified there)
+        const auto y = rows4[max(nb[o], 0)];      // (-1 only in the walk's lists, next to rows whose d2 overflows: output unspecified there)
         const double dd[3] = {((double)y.x - (double)p.x) - P.mu[0], ((double)y.y - (double)p.y) - P.mu[1], ((double)y.z - (double)p.z) - P.mu[2]};
         nrm_cov_add(C6, dd);
     }
@@ -139,22 +234,24 @@ __device__ __forceinline__ void nrm_point(const typename V4<T>::type* __restrict
     P.s = nrm_sign(P.v, dv);
 }
 
-template <typename T>
+template <typename T, bool GRID>
 __global__ __launch_bounds__(BLOCK) void normals_point_kernel(const typename V4<T>::type* __restrict__ tgs4, const int32_t* __restrict__ tperm,
-                                                              const int32_t* __restrict__ rows, int N, int m, int m_pad, int k, int bpc,
-                                                              const int32_t* __restrict__ nbr_s, const T* __restrict__ vp, int vp_stride,
+                                                              const int32_t* __restrict__ rows, const void* __restrict__ plans, int N, int m, int m_pad,
+                                                              int k, int bpc, const int32_t* __restrict__ nbr_s, const T* __restrict__ vp, int vp_stride,
                                                               T* __restrict__ nrm, T* __restrict__ curv) {
     int b, blk;
     if (!decode_block(bpc, N, b, blk)) return;
-    const int mb = rows_of(rows, b, m);
+    const int mb = nrm_live_rows<T, GRID>(rows, plans, b, m);
     const int s = blk * BLOCK + threadIdx.x;
     if (s >= m) return;
     const size_t base = (size_t)b * m_pad;
-    const int k_eff = min(k, mb);
-    const size_t orow = (size_t)b * m + (s < mb ? tperm[base + s] : s);    // the padding's rows: row s itself (original order)
+    const bool live = s < mb;
+    const int k_eff = live ? nrm_k_eff<GRID>(nbr_s + (base + s) * k, k, mb) : 0;
+    // the rows that take no part: the walk's padding is row s itself (original order), the grid's slots cnt .. m - 1 hold their rows
+    const size_t orow = (size_t)b * m + (GRID ? min(max(tperm[base + s], 0), m - 1) : (live ? tperm[base + s] : s));
     T n[3] = {T(0), T(0), T(0)};
     T cv = T(0);
-    if (s < mb && k_eff >= 3) {
+    if (live && k_eff >= 3) {
         NrmPoint P;
         nrm_point<T>(tgs4 + base, nbr_s + (base + s) * k, k_eff, tgs4[base + s], vp ? vp + (size_t)b * vp_stride : nullptr, P);
         n[0] = (T)(P.s * P.v[0]); n[1] = (T)(P.s * P.v[1]); n[2] = (T)(P.s * P.v[2]);
@@ -165,25 +262,25 @@ __global__ __launch_bounds__(BLOCK) void normals_point_kernel(const typename V4<
 }
 
 // ------------------------------------------------------------------ backward
-template <typename T>
+template <typename T, bool GRID>
 __global__ __launch_bounds__(BLOCK) void normals_bwd_kernel(const typename V4<T>::type* __restrict__ tgs4, const int32_t* __restrict__ tperm,
-                                                            const int32_t* __restrict__ rows, int N, int m, int m_pad, int k, int bpc,
-                                                            const int32_t* __restrict__ nbr_s, const T* __restrict__ vp, int vp_stride,
+                                                            const int32_t* __restrict__ rows, const void* __restrict__ plans, int N, int m, int m_pad,
+                                                            int k, int bpc, const int32_t* __restrict__ nbr_s, const T* __restrict__ vp, int vp_stride,
                                                             const T* __restrict__ g_nrm, const T* __restrict__ g_curv, T* __restrict__ gs /* (N,m_pad,3) sorted */) {
     constexpr int H = BwdHalo<T>::v;
     __shared__ T acc[(BLOCK + 2 * H) * 3];
     int b, blk;
     if (!decode_block(bpc, N, b, blk)) return;
-    const int mb = rows_of(rows, b, m);
+    const int mb = nrm_live_rows<T, GRID>(rows, plans, b, m);
     const int s0 = blk * BLOCK, s = s0 + threadIdx.x;
     if (s0 >= mb) return;                                   // (block-uniform)
     const size_t base = (size_t)b * m_pad;
     const int wlo = max(s0 - H, 0), whi = min(s0 + BLOCK + H, mb), wn = (whi - wlo) * 3;
     for (int e = threadIdx.x; e < wn; e += BLOCK) acc[e] = T(0);
     __syncthreads();
-    const int k_eff = min(k, mb);
+    const int k_eff = s < mb ? nrm_k_eff<GRID>(nbr_s + (base + s) * k, k, mb) : 0;
     if (s < mb && k_eff >= 3) {
-        const size_t orow = (size_t)b * m + tperm[base + s];
+        const size_t orow = (size_t)b * m + (GRID ? min(max(tperm[base + s], 0), m - 1) : tperm[base + s]);
         double gn[3] = {0.0, 0.0, 0.0};
         if (g_nrm) { gn[0] = (double)g_nrm[orow * 3]; gn[1] = (double)g_nrm[orow * 3 + 1]; gn[2] = (double)g_nrm[orow * 3 + 2]; }
         const double gk = g_curv ? (double)g_curv[orow] : 0.0;
@@ -224,6 +321,13 @@ int nrm_check(int dtype, int N, int m, int k, int vp_per_cloud) {
     if (bad_dtype(dtype)) return DICP_ERR_DTYPE;
     if (N <= 0 || m <= 0 || k < 3 || k > NRM_KMAX || (vp_per_cloud != 0 && vp_per_cloud != 1)) return DICP_ERR_SHAPE;
     if ((size_t)dicp_padded_targets(m) > 0x7fffffffu / NRM_KMAX) return DICP_ERR_SHAPE;
+    return 0;
+}
+
+int nrm_grid_check(int dtype, int N, int m, int k, int c, int vp_per_cloud) {
+    int rc = nrm_check(dtype, N, m, k, vp_per_cloud);
+    if (rc || (rc = ball_check(dtype, N, m))) return rc;
+    if (c < 3 || (size_t)ball_slots(m) > 0x7fffffffu / NRM_KMAX) return DICP_ERR_SHAPE;
     return 0;
 }
 
@@ -273,7 +377,7 @@ int dicp_normals_forward(int dtype, const void* pts, int c, const int32_t* rows,
 #define DICP_NRM(T) do { \
         const int kc = topk_kcap(k < 8 ? 8 : k);   /* (no list below 8) */ \
         if (kc == 8) DICP_NRM_KNN(T, 8); else if (kc == 16) DICP_NRM_KNN(T, 16); else DICP_NRM_KNN(T, 32); \
-        normals_point_kernel<T><<<g, BLOCK, 0, st>>>((const V4<T>::type*)(ws + L.tgs4), tperm, rows, N, m, m_pad, k, bpc, nbr_s, (const T*)viewpoint, vs, \
+        normals_point_kernel<T, false><<<g, BLOCK, 0, st>>>((const V4<T>::type*)(ws + L.tgs4), tperm, rows, nullptr, N, m, m_pad, k, bpc, nbr_s, (const T*)viewpoint, vs, \
                                                       (T*)normals, (T*)curvature); } while (0)
     if (dtype == DICP_F32) DICP_NRM(float); else DICP_NRM(double);
 #undef DICP_NRM
@@ -303,10 +407,85 @@ int dicp_normals_backward(int dtype, const void* g_normals, const void* g_curvat
     const unsigned g = grid_for(N, bpc);
     const int vs = vp_per_cloud ? 3 : 0;
     begin_launch();
-#define DICP_NRM_BWD(T) normals_bwd_kernel<T><<<g, BLOCK, 0, st>>>((const V4<T>::type*)(ws + L.tgs4), tperm, rows, N, m, m_pad, k, bpc, \
+#define DICP_NRM_BWD(T) normals_bwd_kernel<T, false><<<g, BLOCK, 0, st>>>((const V4<T>::type*)(ws + L.tgs4), tperm, rows, nullptr, N, m, m_pad, k, bpc, \
         (const int32_t*)(ws + L.nbr_s), (const T*)viewpoint, vs, (const T*)g_normals, (const T*)g_curvature, (T*)workspace)
     if (dtype == DICP_F32) DICP_NRM_BWD(float); else DICP_NRM_BWD(double);
 #undef DICP_NRM_BWD
     if ((rc = launch_status())) return rc;
     return dicp_permute_add_rows(dtype, workspace, tperm, N, m_pad, m_pad, m_pad, 3, 3, grad_pts, m, c, stream);
+}
+
+size_t dicp_normals_grid_workspace_bytes(int dtype, int N, int m, int k, int c, int backward) {
+    if (nrm_grid_check(dtype, N, m, k, c, 0)) return 0;
+    const size_t ts = dtype == DICP_F32 ? 4 : 8;
+    if (backward) return up256((size_t)N * ball_slots(m) * 3 * ts);
+    return nrm_grid_layout(dtype, N, m, k).total;
+}
+
+int dicp_normals_grid_forward(int dtype, const void* pts, int c, const int32_t* rows, int N, int m, int k, const void* viewpoint, int vp_per_cloud,
+                              void* normals, void* curvature, int64_t* neighbors, void* workspace, size_t workspace_bytes,
+                              unsigned long long* visited, unsigned long long* passes, void* stream) {
+    if (!pts || !normals || !workspace) return DICP_ERR_NULL;
+    int rc = nrm_grid_check(dtype, N, m, k, c, vp_per_cloud);
+    if (rc) return rc;
+    const NrmGridLayout L = nrm_grid_layout(dtype, N, m, k);
+    if (workspace_bytes < L.total) return DICP_ERR_SHAPE;
+    const size_t ts = dtype == DICP_F32 ? 4 : 8;
+    if ((uintptr_t)workspace % 256 || (uintptr_t)pts % ts || (rows && (uintptr_t)rows % 4) || (uintptr_t)normals % ts ||
+        (curvature && (uintptr_t)curvature % ts) || (neighbors && (uintptr_t)neighbors % 8) || (viewpoint && (uintptr_t)viewpoint % ts) ||
+        (visited && (uintptr_t)visited % 8) || (passes && (uintptr_t)passes % 8)) return DICP_ERR_ALIGN;
+    hipStream_t st = (hipStream_t)stream;
+    char* ws = (char*)workspace;
+    void* plans = ws + L.plans;
+    uint64_t* keys = (uint64_t*)(ws + L.keys);
+    int32_t* perm = (int32_t*)(ws + L.perm);
+    int32_t* nbr_s = (int32_t*)(ws + L.nbr_s);
+    if (visited && (rc = dicp_fill::zero(visited, (size_t)N * sizeof(unsigned long long), st))) return rc;
+    if (passes && (rc = dicp_fill::zero(passes, (size_t)N * sizeof(unsigned long long), st))) return rc;
+    const int P = ball_slots(m);
+    const int bpc = (m + BLOCK - 1) / BLOCK;
+    const unsigned g = grid_for(N, bpc);
+    const int vs = vp_per_cloud ? 3 : 0;
+    begin_launch();
+#define DICP_NRM_GKNN(T, KK) normals_grid_knn_kernel<T, KK><<<g, BLOCK, 0, st>>>(plans, keys, perm, (const V4<T>::type*)(ws + L.rows4), N, m, P, k, bpc, \
+        nbr_s, neighbors, visited, passes)
+#define DICP_NRM_GRID(T) do { \
+        if ((rc = gknn_grid_build<T>((const T*)pts, c, rows, N, m, plans, keys, perm, ws + L.rows4, st))) return rc; \
+        const int kc = topk_kcap(k < 8 ? 8 : k);   /* (no list below 8) */ \
+        if (kc == 8) DICP_NRM_GKNN(T, 8); else if (kc == 16) DICP_NRM_GKNN(T, 16); else DICP_NRM_GKNN(T, 32); \
+        normals_point_kernel<T, true><<<g, BLOCK, 0, st>>>((const V4<T>::type*)(ws + L.rows4), perm, nullptr, plans, N, m, P, k, bpc, nbr_s, \
+                                                           (const T*)viewpoint, vs, (T*)normals, (T*)curvature); } while (0)
+    if (dtype == DICP_F32) DICP_NRM_GRID(float); else DICP_NRM_GRID(double);
+#undef DICP_NRM_GRID
+#undef DICP_NRM_GKNN
+    return launch_status();
+}
+
+int dicp_normals_grid_backward(int dtype, const void* g_normals, const void* g_curvature, const void* viewpoint, int vp_per_cloud,
+                               int N, int m, int k, int c, const void* fwd_workspace, void* grad_pts, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!fwd_workspace || !grad_pts || !workspace) return DICP_ERR_NULL;
+    int rc = nrm_grid_check(dtype, N, m, k, c, vp_per_cloud);
+    if (rc) return rc;
+    if (workspace_bytes < dicp_normals_grid_workspace_bytes(dtype, N, m, k, c, 1)) return DICP_ERR_SHAPE;
+    const size_t ts = dtype == DICP_F32 ? 4 : 8;
+    if ((uintptr_t)fwd_workspace % 256 || (uintptr_t)workspace % 16 || (uintptr_t)grad_pts % ts || (g_normals && (uintptr_t)g_normals % ts) ||
+        (g_curvature && (uintptr_t)g_curvature % ts) || (viewpoint && (uintptr_t)viewpoint % ts)) return DICP_ERR_ALIGN;
+    hipStream_t st = (hipStream_t)stream;
+    const NrmGridLayout L = nrm_grid_layout(dtype, N, m, k);
+    const char* ws = (const char*)fwd_workspace;
+    const int P = ball_slots(m);
+    const int32_t* perm = (const int32_t*)(ws + L.perm);
+    if ((rc = dicp_fill::zero(workspace, (size_t)N * P * 3 * ts, st))) return rc;
+    if ((rc = dicp_fill::zero(grad_pts, (size_t)N * m * c * ts, st))) return rc;
+    if (!g_normals && !g_curvature) return 0;
+    const int bpc = (m + BLOCK - 1) / BLOCK;
+    const unsigned g = grid_for(N, bpc);
+    const int vs = vp_per_cloud ? 3 : 0;
+    begin_launch();
+#define DICP_NRM_BWD(T) normals_bwd_kernel<T, true><<<g, BLOCK, 0, st>>>((const V4<T>::type*)(ws + L.rows4), perm, nullptr, ws + L.plans, N, m, P, k, bpc, \
+        (const int32_t*)(ws + L.nbr_s), (const T*)viewpoint, vs, (const T*)g_normals, (const T*)g_curvature, (T*)workspace)
+    if (dtype == DICP_F32) DICP_NRM_BWD(float); else DICP_NRM_BWD(double);
+#undef DICP_NRM_BWD
+    if ((rc = launch_status())) return rc;
+    return dicp_permute_add_rows(dtype, workspace, perm, N, m, P, P, 3, 3, grad_pts, m, c, stream);   // (slots 0 .. m - 1 hold the cloud's m rows)
 }

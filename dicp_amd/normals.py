@@ -1,7 +1,8 @@
 """Differentiable surface normals for point-to-plane targets.
 
 `ICP(icp_type='pt2pl')` takes target rows (m, 6) = xyz + unit normal.  `estimate_normals` computes those normals from the points
-alone, on the GPU (libdicp_hip.so: dicp_normals_forward / dicp_normals_backward), with gradients back to the points:
+alone, on the GPU (libdicp_hip.so: dicp_normals_forward / dicp_normals_backward, or dicp_normals_grid_forward / dicp_normals_grid_backward
+with method="grid"), with gradients back to the points:
 
     from dicp_amd.normals import estimate_normals
     nrm = estimate_normals(pts, k=16)
@@ -13,21 +14,23 @@ import torch
 from . import _clouds, _lib
 from ._clouds import ROW
 from ._ops import _DT, _p, _stream, _on, _workspace
+from .knn import _check_method
 
 K_MIN, K_MAX = 3, 32
 
 
 class _Normals(torch.autograd.Function):
     """(N,m,c) points -> (normals (N,m,3), curvature (N,m), neighbours (N,m,k) int64 or None): one library call per direction on the current
-    stream, into one allocation per direction."""
+    stream, into one allocation per direction.  grid: the neighbours from the cloud's cell grid (dicp_normals_grid_*) instead of the
+    x-sorted walk; visited / passes: its optional (N,) int64 counters."""
 
     @staticmethod
-    def forward(ctx, pts, rows, vp, k, want_nbr):
+    def forward(ctx, pts, rows, vp, k, want_nbr, grid, visited, passes):
         N, m, c = pts.shape
         dt = _DT[pts.dtype]
         lib = _lib.load()
         ts = pts.element_size()
-        ws_bytes = lib.dicp_normals_workspace_bytes(dt, N, m, k, c, 0)
+        ws_bytes = (lib.dicp_normals_grid_workspace_bytes if grid else lib.dicp_normals_workspace_bytes)(dt, N, m, k, c, 0)
         up = lambda x: (x + 255) // 256 * 256
         o_nrm, o_curv = 0, up(N * m * 3 * ts)
         o_nbr = o_curv + up(N * m * ts)
@@ -37,12 +40,17 @@ class _Normals(torch.autograd.Function):
         curv = buf[o_curv: o_curv + N * m * ts].view(pts.dtype).view(N, m)
         nbr = buf[o_nbr: o_nbr + N * m * k * 8].view(torch.int64).view(N, m, k) if want_nbr else None
         ws = buf[o_ws:]
+        per_cloud = int(vp is not None and vp.dim() == 2)
         with _on(pts.device):
-            _lib.check(lib.dicp_normals_forward(dt, _p(pts), c, _p(rows), N, m, k, _p(vp), int(vp is not None and vp.dim() == 2),
-                                                _p(nrm), _p(curv), _p(nbr), _p(ws), ws_bytes, None, _stream()), "dicp_normals_forward")
+            if grid:
+                _lib.check(lib.dicp_normals_grid_forward(dt, _p(pts), c, _p(rows), N, m, k, _p(vp), per_cloud, _p(nrm), _p(curv), _p(nbr),
+                                                         _p(ws), ws_bytes, _p(visited), _p(passes), _stream()), "dicp_normals_grid_forward")
+            else:
+                _lib.check(lib.dicp_normals_forward(dt, _p(pts), c, _p(rows), N, m, k, _p(vp), per_cloud,
+                                                    _p(nrm), _p(curv), _p(nbr), _p(ws), ws_bytes, None, _stream()), "dicp_normals_forward")
         ctx.save_for_backward(rows, vp)
         ctx.ws = ws                                     # (a view of the outputs' allocation: kept off the saved-tensor version checks)
-        ctx.shape, ctx.k = (N, m, c), k
+        ctx.shape, ctx.k, ctx.grid = (N, m, c), k, grid
         ctx.set_materialize_grads(False)
         if nbr is not None:
             ctx.mark_non_differentiable(nbr)
@@ -51,7 +59,7 @@ class _Normals(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_nrm, g_curv, _g_nbr):
         if g_nrm is None and g_curv is None:
-            return None, None, None, None, None
+            return (None,) * 8
         rows, vp = ctx.saved_tensors
         ws = ctx.ws
         N, m, c = ctx.shape
@@ -59,26 +67,40 @@ class _Normals(torch.autograd.Function):
         dt = _DT[dtype]
         lib = _lib.load()
         ts = torch.empty((), dtype=dtype).element_size()
-        g_bytes = lib.dicp_normals_workspace_bytes(dt, N, m, ctx.k, c, 1)
+        g_bytes = (lib.dicp_normals_grid_workspace_bytes if ctx.grid else lib.dicp_normals_workspace_bytes)(dt, N, m, ctx.k, c, 1)
         o_gws = (N * m * c * ts + 255) // 256 * 256
         buf = _workspace(o_gws + g_bytes, ws.device)
         grad = buf[:N * m * c * ts].view(dtype).view(N, m, c)
         gws = buf[o_gws:]
         g_nrm = g_nrm.contiguous() if g_nrm is not None else None
         g_curv = g_curv.contiguous() if g_curv is not None else None
+        per_cloud = int(vp is not None and vp.dim() == 2)
         with _on(ws.device):
-            _lib.check(lib.dicp_normals_backward(dt, _p(g_nrm), _p(g_curv), _p(vp), int(vp is not None and vp.dim() == 2), _p(rows), N, m, ctx.k, c,
-                                                 _p(ws), _p(grad), _p(gws), gws.numel(), _stream()), "dicp_normals_backward")
-        return grad, None, None, None, None
+            if ctx.grid:
+                _lib.check(lib.dicp_normals_grid_backward(dt, _p(g_nrm), _p(g_curv), _p(vp), per_cloud, N, m, ctx.k, c,
+                                                          _p(ws), _p(grad), _p(gws), gws.numel(), _stream()), "dicp_normals_grid_backward")
+            else:
+                _lib.check(lib.dicp_normals_backward(dt, _p(g_nrm), _p(g_curv), _p(vp), per_cloud, _p(rows), N, m, ctx.k, c,
+                                                     _p(ws), _p(grad), _p(gws), gws.numel(), _stream()), "dicp_normals_backward")
+        return (grad,) + (None,) * 7
 
 
-def estimate_normals(points, k=16, viewpoint=None, rows=None, return_curvature=False, return_neighbors=False):
+def estimate_normals(points, k=16, viewpoint=None, rows=None, return_curvature=False, return_neighbors=False, method="walk",
+                     _visited=None, _passes=None):
     """Unit surface normals of every point from its k nearest neighbours in its own cloud.
 
     points: (m, c), (N, m, c) with c >= 3 (columns 0:3 are used), or a list of (m_b, c); float32 or float64.  CPU tensors are computed on the
         GPU and returned on the CPU.
     k: 3 <= k <= 32.  rows: optional (N,) row counts of a padded batch (as ICP.icp's target_rows); rows past them are padding.
     viewpoint: None (the origin, as for a scan in its sensor frame), (3,) or (N, 3): each normal is flipped to face it.
+    method: "walk" (the default) searches the neighbours along the x-sorted cloud; "grid" sorts the cloud into a cell grid whose cell edge is
+        chosen on the device from the cloud's own density (as knn_points(method="grid"); the proof is csrc/dicp_gridknn.h) and lets every
+        point grow a box of cells until its k-th distance is proved final.  Both are exact: on every cloud the walk defines -- all rows
+        below the row count finite, no d2 that overflows -- they return the same neighbour lists and the same bits of normals and
+        curvature, and differ in speed only (README, "Surface normals").  Where the walk leaves its output unspecified, "grid" follows
+        knn_points' rule: the candidates of point i are the rows below the row count with three finite coordinates whose d2 to i is
+        finite, and k_eff(i) = min(k, their number); a row with a non-finite coordinate is nobody's neighbour and gets a zero normal,
+        zero curvature, -1 neighbours and no gradient; k_eff(i) < 3 gives the zero normal.  Nothing is read back from the device.
 
     Definition (what the tests pin): the neighbours of point i are the k_eff = min(k, rows_b) rows of its cloud first in (d2, index) order, i itself
     among them, d2 = (dx*dx + dy*dy) + dz*dz; C = (1/k_eff) sum (q_j - mu)(q_j - mu)^T with q_j = p_j - p_i and mu = mean q; the normal is C's
@@ -95,6 +117,7 @@ def estimate_normals(points, k=16, viewpoint=None, rows=None, return_curvature=F
     points there.  The backward sums through float atomics, so its result is not bit-reproducible from run to run.
     """
     _clouds._check_k(k, "estimate_normals", K_MIN, K_MAX)
+    _check_method(method, "estimate_normals")
     form, batch, rows, lens = _clouds.check(points, rows, "estimate_normals", flat_rows=True)
     N, m = batch.shape[0], batch.shape[1]
     vp = None
@@ -105,7 +128,7 @@ def estimate_normals(points, k=16, viewpoint=None, rows=None, return_curvature=F
 
     on_cpu, x, rows_d = _clouds.place(batch, rows)
     vp_d = vp.detach().to(device=x.device, dtype=x.dtype).contiguous() if vp is not None else None
-    nrm, curv, nbr = _Normals.apply(x, rows_d, vp_d, k, bool(return_neighbors))
+    nrm, curv, nbr = _Normals.apply(x, rows_d, vp_d, k, bool(return_neighbors), method == "grid", _visited, _passes)
     outs = [(ROW, nrm)] + ([(ROW, curv)] if return_curvature else []) + ([(ROW, nbr)] if return_neighbors else [])
     outs = _clouds.restore(form, on_cpu, m, lens, outs)
     return outs[0] if len(outs) == 1 else outs

@@ -838,6 +838,24 @@ int dicp_normals_forward(int dtype, const void* pts, int c, const int32_t* rows,
 int dicp_normals_backward(int dtype, const void* g_normals, const void* g_curvature, const void* viewpoint, int vp_per_cloud, const int32_t* rows,
                           int N, int m, int k, int c, const void* fwd_workspace, void* grad_pts, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The same normals with the neighbours searched on the cloud's own cell grid (estimate_normals with method="grid"; the grid and the
+ * scan: dicp_knn_grid_build / csrc/dicp_gridknn.h).  Arguments as dicp_normals_*; the differences:
+ *   The candidates of point i are the rows j < rows[b] with three finite coordinates whose d2 to i is finite, k_eff(i) = min(k, their
+ *   number), the list their first k_eff(i) in (d2, index) order.  A row with a non-finite coordinate is nobody's neighbour and gets a zero
+ *   normal, zero curvature, -1 neighbours and no gradient, as a pad row does; so does a point with k_eff(i) < 3.  On a cloud whose live
+ *   rows are finite and whose d2 never overflows the lists are dicp_normals_forward's, and normals and curvature are its bits.
+ * dicp_normals_grid_workspace_bytes: as dicp_normals_workspace_bytes, for these two entry points.
+ * dicp_normals_grid_forward: the workspace (256-byte aligned) holds the grid (plans, keys, perm, rows4) and the neighbour slots: keep it
+ *   unchanged until the backward.  visited / passes: optional (N) counters of the rows the scans were fed and the boxes they computed
+ *   (diagnostics; zeroed first).  Nothing is read back; every launch is capturable.
+ * dicp_normals_grid_backward: as dicp_normals_backward (the live rows come from the workspace's plans, so there is no rows argument). */
+size_t dicp_normals_grid_workspace_bytes(int dtype, int N, int m, int k, int c, int backward);
+int dicp_normals_grid_forward(int dtype, const void* pts, int c, const int32_t* rows, int N, int m, int k, const void* viewpoint, int vp_per_cloud,
+                              void* normals, void* curvature, int64_t* neighbors, void* workspace, size_t workspace_bytes,
+                              unsigned long long* visited, unsigned long long* passes, void* stream);
+int dicp_normals_grid_backward(int dtype, const void* g_normals, const void* g_curvature, const void* viewpoint, int vp_per_cloud,
+                               int N, int m, int k, int c, const void* fwd_workspace, void* grad_pts, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Voxel-grid downsampling (dicp_amd/voxel.py).
  *   pts (N,m,c) T, c >= 3; rows: optional (N) row counts as tgt_rows.  Row r of cloud b takes part when r < rows[b] and its x, y, z are finite.
  *   v_d = floor((p_d - o_d) / s_d) in T (o and s converted to T first; one rounded subtraction, one IEEE division); |v_d| >= 2^62 fails the cloud,
