@@ -1,7 +1,8 @@
-"""The cloud arguments of the point-cloud operators (normals, voxel, knn, fps, ball): one cloud, a padded batch with row counts, or a list.
+"""The cloud arguments of the point-cloud operators (normals, voxel, knn, fps, ball, group): one cloud, a padded batch with row counts, or a list.
 
-check / check_pair validate on the host (no device is touched), place moves a checked batch to the compute device, restore cuts the
-library's (N, ...) results back to the caller's form and device.  What differs between the operators is an argument at their call site.
+check / check_pair / check_slots validate on the host (no device is touched), place moves a checked batch to the compute device, restore
+cuts the library's (N, ...) results back to the caller's form and device.  What differs between the operators is an argument at their call
+site.
 """
 import torch
 
@@ -19,25 +20,26 @@ def _check_k(k, what, lo, hi):
         _err(what, "k must be an int in [%d, %d], got %r" % (lo, hi, k))
 
 
-def _check_points(t, name, what):
+def _check_points(t, name, what, min_cols=3):
     if not isinstance(t, torch.Tensor):
         _err(what, "%s must be a tensor, got %s" % (name, type(t).__name__))
     if t.dtype not in _DT:
         _err(what, "%s must be float32 or float64, got %s" % (name, t.dtype))
-    if t.dim() < 1 or t.shape[-1] < 3:
-        _err(what, "%s needs at least 3 columns (x, y, z), got shape %s" % (name, tuple(t.shape)))
+    if t.dim() < 1 or t.shape[-1] < min_cols:
+        _err(what, "%s needs at least %s, got shape %s" % (name, "3 columns (x, y, z)" if min_cols == 3 else "%d column(s)" % min_cols, tuple(t.shape)))
 
 
-def check(t, rows, what, name="points", rows_name="rows", empty_ok=False, flat_rows=False):
+def check(t, rows, what, name="points", rows_name="rows", empty_ok=False, flat_rows=False, min_cols=3):
     """-> (form, batch (N,m,c), rows or None, lengths of a list or None); ValueError for anything invalid.
 
     empty_ok: clouds without rows are let through (place pads them).  flat_rows: rows may have any shape with N elements, a single cloud
-    (N = 1) included; otherwise they are 1-D and need a padded batch."""
+    (N = 1) included; otherwise they are 1-D and need a padded batch.  min_cols: the fewest columns a table may have (3: points; 1: a
+    feature table, a per-point weight)."""
     if isinstance(t, (list, tuple)):
         if not t:
             _err(what, "%s is an empty list" % name)
         for i, c in enumerate(t):
-            _check_points(c, "%s[%d]" % (name, i), what)
+            _check_points(c, "%s[%d]" % (name, i), what, min_cols)
             if c.dim() != 2:
                 _err(what, "%s[%d] must be (m_b, c), got shape %s" % (name, i, tuple(c.shape)))
         if len({c.shape[1] for c in t}) != 1 or len({c.dtype for c in t}) != 1 or len({c.device for c in t}) != 1:
@@ -47,7 +49,7 @@ def check(t, rows, what, name="points", rows_name="rows", empty_ok=False, flat_r
         lens = [c.shape[0] for c in t]
         form, batch, rows = "list", torch.nn.utils.rnn.pad_sequence(list(t), batch_first=True), torch.tensor(lens, dtype=torch.int32)
     else:
-        _check_points(t, name, what)
+        _check_points(t, name, what, min_cols)
         if t.dim() not in (2, 3):
             _err(what, "%s must be (m, c), (N, m, c) or a list of (m_b, c), got shape %s" % (name, tuple(t.shape)))
         if t.dim() == 2 and rows is not None and not flat_rows:
@@ -80,6 +82,53 @@ def check_pair(x, y, x_rows, y_rows, what):
     if bx.shape[0] != by.shape[0]:
         _err(what, "x and y must hold the same number of clouds, got %d and %d" % (bx.shape[0], by.shape[0]))
     return cx, cy
+
+
+_INT = (torch.int32, torch.int64)
+
+
+def check_slots(t, what, name, like, integer, k_lo, k_hi):
+    """An argument with k slots per row -- the idx / d2 that knn_points and ball_query return: (n, k), (N, n, k) or a list of (n_b, k)
+    -> (batch (N,n,k), lengths of a list or None); ValueError for anything invalid.
+
+    like: the checked form and batch (form, batch) of the argument it goes with: the same form, cloud count and device.  integer: int32 or
+    int64 indices, kept as they are (a list is padded with -1, the empty slot); otherwise the dtype of like's batch (padded with 0)."""
+    form, other = like
+    is_list = isinstance(t, (list, tuple))
+    items = list(t) if is_list else [t]
+    if is_list and not items:
+        _err(what, "%s is an empty list" % name)
+    for i, c in enumerate(items):
+        nm = "%s[%d]" % (name, i) if is_list else name
+        if not isinstance(c, torch.Tensor):
+            _err(what, "%s must be a tensor, got %s" % (nm, type(c).__name__))
+        if integer and c.dtype not in _INT:
+            _err(what, "%s must be int32 or int64, got %s" % (nm, c.dtype))
+        if not integer and c.dtype != other.dtype:
+            _err(what, "%s must have the dtype of the features, %s, got %s" % (nm, other.dtype, c.dtype))
+        if is_list and c.dim() != 2:
+            _err(what, "%s must be (n_b, k), got shape %s" % (nm, tuple(c.shape)))
+    if not is_list and t.dim() not in (2, 3):
+        _err(what, "%s must be (n, k), (N, n, k) or a list of (n_b, k), got shape %s" % (name, tuple(t.shape)))
+    mine = "list" if is_list else ("single" if t.dim() == 2 else "batch")
+    if mine != form:
+        _err(what, "%s must have the form of the features (single clouds, padded batches or lists), got %s and %s" % (name, mine, form))
+    if len({c.shape[-1] for c in items}) != 1 or len({c.dtype for c in items}) != 1 or len({c.device for c in items}) != 1:
+        _err(what, "the clouds of %s need one slot count, dtype and device" % name)
+    k = items[0].shape[-1]
+    if not (k_lo <= k <= k_hi):
+        _err(what, "%s must have k in [%d, %d] slots, got shape %s" % (name, k_lo, k_hi, tuple(items[0].shape)))
+    if items[0].device != other.device:
+        _err(what, "%s and the features must be on one device, got %s and %s" % (name, items[0].device, other.device))
+    if is_list:
+        batch, lens = torch.nn.utils.rnn.pad_sequence(items, batch_first=True, padding_value=-1 if integer else 0), [c.shape[0] for c in items]
+    else:
+        batch, lens = (t.unsqueeze(0) if t.dim() == 2 else t), None
+    if batch.shape[0] != other.shape[0]:
+        _err(what, "%s and the features must hold the same number of clouds, got %d and %d" % (name, batch.shape[0], other.shape[0]))
+    if batch.shape[1] < 1:
+        _err(what, "%s has no rows, shape %s" % (name, tuple(batch.shape)))
+    return batch, lens
 
 
 def place(batch, rows, xyz=False):

@@ -1,0 +1,397 @@
+// Neighbourhood features (dicp_amd/group.py): gather and interpolate the rows of a feature table (N,m,C) through the (N,n,k) index
+// tensors of ball_query / knn_points, with their backward passes.  The per-slot rules are csrc/dicp_group.h's.
+//
+// All of it is memory traffic, so the kernels differ only in how threads are laid over it.  Two forms, chosen on the host by the row size:
+//   wide   (C * sizeof(T) >= 128 bytes): ONE WAVE PER QUERY.  Lanes 0..k-1 load the query's k indices once and turn them into row numbers
+//          (-1: empty); the wave reads them by shuffles in wave-uniform loops.  Lanes then run along the channels, so a gathered row and an
+//          output row are one contiguous segment each; 16-byte accesses where C * sizeof(T) and the bases are multiples of 16 (V > 1),
+//          otherwise one element per lane (V = 1: C = 33, 65, 130, or a misaligned view).  group_points lays its lanes over the query's
+//          whole (slot, channel) block, which is contiguous in the output.
+//   narrow (C = 1, 3, 4, 6 ...): lanes over the flattened (query, slot, channel) / (query, channel) / (query, slot) space, so that stores
+//          stay contiguous; a wave per query would leave most of its lanes idle.
+// Backward into the features is a scatter-add with float atomics (unsafeAtomicAdd: one global_atomic_add per element, no compare-and-swap
+// loop), one element per lane: a wave adds 256 contiguous bytes of one row at C = 64 float32.  group_points' backward is flat in both
+// forms -- consecutive lanes are consecutive (slot, channel) elements, the same addresses a wave per query would add to.  g_centers and
+// g_d2 are written once per element without atomics; g_d2's channel sum is per-lane partial sums in channel order, then a butterfly.
+// Every kernel is a grid-stride loop of at most GROUP_MAX_BLOCKS workgroups with 64-bit element counts.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "dicp_common.h"
+#include "dicp_fill.h"
+#include "dicp_group.h"
+
+namespace {
+
+constexpr int GW = BLOCK / WAVE;                    // waves (queries in flight) per workgroup of the wide form
+constexpr unsigned GROUP_MAX_BLOCKS = 2048;         // 8 workgroups of 4 waves on each of 256 CUs: every wave slot of the chip
+constexpr size_t GROUP_WIDE_BYTES = 128;
+static_assert(GROUP_K_MAX <= WAVE, "a query's slots fit the lanes of one wave");
+
+template <typename T, int V>
+struct alignas(sizeof(T) * V) Pack { T v[V]; };
+
+template <typename T, int V>
+__device__ __forceinline__ Pack<T, V> pack_load(const T* p) { return *reinterpret_cast<const Pack<T, V>*>(p); }
+template <typename T, int V>
+__device__ __forceinline__ void pack_store(T* p, const Pack<T, V>& x) { *reinterpret_cast<Pack<T, V>*>(p) = x; }
+
+inline unsigned group_grid(size_t items, int per_block) {
+    const size_t g = (items + per_block - 1) / per_block;
+    return (unsigned)(g < 1 ? 1 : (g > GROUP_MAX_BLOCKS ? GROUP_MAX_BLOCKS : g));
+}
+
+// lane s < k: the row of slot s of query q (-1: empty); -1 in the other lanes
+template <typename I>
+__device__ __forceinline__ int lane_row(const I* __restrict__ idx, size_t q, int k, int lane, int nb) {
+    return lane < k ? group_row(idx[q * k + lane], nb) : -1;
+}
+
+template <typename T>
+__device__ __forceinline__ T wave_sum(T x) {
+#pragma unroll
+    for (int off = WAVE / 2; off > 0; off >>= 1) x = x + __shfl_xor(x, off);
+    return x;
+}
+
+// ------------------------------------------------------------------ group_points
+template <typename T, typename I, int V>
+__global__ __launch_bounds__(BLOCK) void group_fwd_wide_kernel(const T* __restrict__ f, const I* __restrict__ idx, const int32_t* __restrict__ rows,
+                                                               const T* __restrict__ cen, int Cc, size_t Q, int n, int m, int k, int C, T* __restrict__ out) {
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int VR = C / V, items = k * VR;
+    for (size_t q = (size_t)blockIdx.x * GW + threadIdx.x / WAVE; q < Q; q += (size_t)gridDim.x * GW) {
+        const size_t b = q / n;
+        const int jr = lane_row(idx, q, k, lane, rows_of(rows, (int)b, m));
+        const T* F = f + b * m * C;
+        T* O = out + q * k * C;
+        for (int i0 = 0; i0 < items; i0 += WAVE) {          // (wave-uniform trips: the shuffle needs every lane)
+            const int item = i0 + lane;
+            const bool on = item < items;
+            const int s = on ? item / VR : 0;
+            const int j = __shfl(jr, s);
+            if (!on) continue;
+            const int c = (item - s * VR) * V;
+            Pack<T, V> x;
+#pragma unroll
+            for (int e = 0; e < V; ++e) x.v[e] = T(0);
+            if (j >= 0) {
+                x = pack_load<T, V>(F + (size_t)j * C + c);
+#pragma unroll
+                for (int e = 0; e < V; ++e)
+                    if (c + e < Cc) x.v[e] = group_value<T>(x.v[e], cen[q * Cc + c + e], true);
+            }
+            pack_store<T, V>(O + (size_t)item * V, x);
+        }
+    }
+}
+
+template <typename T, typename I>
+__global__ __launch_bounds__(BLOCK) void group_fwd_narrow_kernel(const T* __restrict__ f, const I* __restrict__ idx, const int32_t* __restrict__ rows,
+                                                                 const T* __restrict__ cen, int Cc, size_t total, int n, int m, int k, int C, T* __restrict__ out) {
+    for (size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x; i < total; i += (size_t)gridDim.x * BLOCK) {
+        const size_t slot = i / C;
+        const int c = (int)(i - slot * C);
+        const size_t q = slot / k, b = q / n;
+        const int j = group_row(idx[slot], rows_of(rows, (int)b, m));
+        T v = T(0);
+        if (j >= 0) v = group_value<T>(f[(b * m + (size_t)j) * C + c], c < Cc ? cen[q * Cc + c] : T(0), c < Cc);
+        out[i] = v;
+    }
+}
+
+// g_features (zeroed) += g_out over the live slots: one element per lane, consecutive lanes consecutive (slot, channel) elements
+template <typename T, typename I>
+__global__ __launch_bounds__(BLOCK) void group_bwd_kernel(const T* __restrict__ g, const I* __restrict__ idx, const int32_t* __restrict__ rows,
+                                                          size_t total, int n, int m, int k, int C, T* __restrict__ gf) {
+    for (size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x; i < total; i += (size_t)gridDim.x * BLOCK) {
+        const size_t slot = i / C;
+        const int c = (int)(i - slot * C);
+        const size_t b = slot / k / n;
+        const int j = group_row(idx[slot], rows_of(rows, (int)b, m));
+        if (j >= 0) unsafeAtomicAdd(gf + (b * m + (size_t)j) * C + c, g[i]);
+    }
+}
+
+// g_centers[q, c] = -(sum of g_out[q, s, c] over the live slots in slot order), 0 without a live slot: written once
+template <typename T, typename I>
+__global__ __launch_bounds__(BLOCK) void group_gcenters_kernel(const T* __restrict__ g, const I* __restrict__ idx, const int32_t* __restrict__ rows,
+                                                               int Cc, size_t total, int n, int m, int k, int C, T* __restrict__ gc) {
+    for (size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x; i < total; i += (size_t)gridDim.x * BLOCK) {
+        const size_t q = i / Cc;
+        const int c = (int)(i - q * Cc);
+        const int nb = rows_of(rows, (int)(q / n), m);
+        T acc = T(0);
+        int cnt = 0;
+        for (int s = 0; s < k; ++s)
+            if (group_row(idx[q * k + s], nb) >= 0) { acc = acc + g[(q * k + s) * C + c]; ++cnt; }
+        gc[i] = cnt ? -acc : T(0);
+    }
+}
+
+// ------------------------------------------------------------------ interpolate_features
+// lane s < k: the slot's row (-1: empty index or non-finite d2) and r_s (0 for an empty slot); R in every lane, in slot order
+template <typename T, typename I>
+__device__ __forceinline__ void interp_lanes(const I* __restrict__ idx, const T* __restrict__ d2, T eps, size_t q, int k, int lane, int nb, int& jr, T& r, T& R) {
+    jr = lane_row(idx, q, k, lane, nb);
+    r = T(0);
+    if (jr >= 0) {
+        const T d = d2[q * k + lane];
+        if (group_finite(d)) r = interp_r<T>(d, eps); else jr = -1;
+    }
+    R = T(0);
+    for (int s = 0; s < k; ++s) R = R + __shfl(r, s);       // (an empty slot adds 0: exact)
+}
+
+// the same for one thread: R over the query's slots
+template <typename T, typename I>
+__device__ __forceinline__ int interp_slot(const I* __restrict__ idx, const T* __restrict__ d2, T eps, size_t o, int nb, T& r) {
+    int j = group_row(idx[o], nb);
+    r = T(0);
+    if (j >= 0) {
+        const T d = d2[o];
+        if (group_finite(d)) r = interp_r<T>(d, eps); else j = -1;
+    }
+    return j;
+}
+
+template <typename T, typename I, int V>
+__global__ __launch_bounds__(BLOCK) void interp_fwd_wide_kernel(const T* __restrict__ f, const I* __restrict__ idx, const int32_t* __restrict__ rows, const T* __restrict__ d2, T eps,
+                                                                size_t Q, int n, int m, int k, int C, T* __restrict__ out) {
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int VR = C / V;
+    for (size_t q = (size_t)blockIdx.x * GW + threadIdx.x / WAVE; q < Q; q += (size_t)gridDim.x * GW) {
+        const size_t b = q / n;
+        int jr;
+        T r, R;
+        interp_lanes<T, I>(idx, d2, eps, q, k, lane, rows_of(rows, (int)b, m), jr, r, R);
+        const T w = interp_w<T>(r, R);
+        const T* F = f + b * m * C;
+        for (int v0 = 0; v0 < VR; v0 += WAVE) {
+            const bool on = v0 + lane < VR;
+            const int c = (v0 + lane) * V;
+            Pack<T, V> acc;
+#pragma unroll
+            for (int e = 0; e < V; ++e) acc.v[e] = T(0);
+            for (int s = 0; s < k; ++s) {
+                const int j = __shfl(jr, s);
+                const T ws = __shfl(w, s);
+                if (j < 0 || !on) continue;
+                const Pack<T, V> x = pack_load<T, V>(F + (size_t)j * C + c);
+#pragma unroll
+                for (int e = 0; e < V; ++e) acc.v[e] = interp_add<T>(acc.v[e], ws, x.v[e]);
+            }
+            if (on) pack_store<T, V>(out + q * C + c, acc);
+        }
+    }
+}
+
+template <typename T, typename I>
+__global__ __launch_bounds__(BLOCK) void interp_fwd_narrow_kernel(const T* __restrict__ f, const I* __restrict__ idx, const int32_t* __restrict__ rows, const T* __restrict__ d2, T eps,
+                                                                  size_t total, int n, int m, int k, int C, T* __restrict__ out) {
+    for (size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x; i < total; i += (size_t)gridDim.x * BLOCK) {
+        const size_t q = i / C;
+        const int c = (int)(i - q * C);
+        const size_t b = q / n;
+        const int nb = rows_of(rows, (int)b, m);
+        T R = T(0), r;
+        for (int s = 0; s < k; ++s) {
+            interp_slot<T, I>(idx, d2, eps, q * k + s, nb, r);
+            R = R + r;
+        }
+        T acc = T(0);
+        for (int s = 0; s < k; ++s) {
+            const int j = interp_slot<T, I>(idx, d2, eps, q * k + s, nb, r);
+            if (j >= 0) acc = interp_add<T>(acc, interp_w<T>(r, R), f[(b * m + (size_t)j) * C + c]);
+        }
+        out[i] = acc;
+    }
+}
+
+// gf (zeroed, optional) += w_s g_out; gd2 (optional) written once per slot by lane 0 of the query's wave
+template <typename T, typename I>
+__global__ __launch_bounds__(BLOCK) void interp_bwd_wide_kernel(const T* __restrict__ g, const T* __restrict__ f, const T* __restrict__ out, const I* __restrict__ idx,
+                                                                const int32_t* __restrict__ rows, const T* __restrict__ d2, T eps, size_t Q, int n, int m, int k, int C,
+                                                                T* __restrict__ gf, T* __restrict__ gd2) {
+    const int lane = threadIdx.x & (WAVE - 1);
+    for (size_t q = (size_t)blockIdx.x * GW + threadIdx.x / WAVE; q < Q; q += (size_t)gridDim.x * GW) {
+        const size_t b = q / n;
+        int jr;
+        T r, R;
+        interp_lanes<T, I>(idx, d2, eps, q, k, lane, rows_of(rows, (int)b, m), jr, r, R);
+        const T w = interp_w<T>(r, R);
+        const T* F = f + b * m * C;
+        const T* G = g + q * C;
+        const T* O = out + q * C;
+        for (int s = 0; s < k; ++s) {
+            const int j = __shfl(jr, s);                    // (wave-uniform, and so is the branch below)
+            const T ws = __shfl(w, s), rs = __shfl(r, s);
+            if (j < 0) {
+                if (gd2 && lane == 0) gd2[q * k + s] = T(0);
+                continue;
+            }
+            T dot = T(0);
+            for (int c = lane; c < C; c += WAVE) {
+                const T gc = G[c];
+                if (gd2) dot = interp_dot_add<T>(dot, gc, F[(size_t)j * C + c], O[c]);
+                if (gf) unsafeAtomicAdd(gf + (b * m + (size_t)j) * C + c, ws * gc);
+            }
+            if (gd2) {
+                dot = wave_sum(dot);
+                if (lane == 0) gd2[q * k + s] = interp_gd2<T>(rs, R, dot);
+            }
+        }
+    }
+}
+
+// one thread per (query, slot)
+template <typename T, typename I>
+__global__ __launch_bounds__(BLOCK) void interp_bwd_narrow_kernel(const T* __restrict__ g, const T* __restrict__ f, const T* __restrict__ out, const I* __restrict__ idx,
+                                                                  const int32_t* __restrict__ rows, const T* __restrict__ d2, T eps, size_t total, int n, int m, int k, int C,
+                                                                  T* __restrict__ gf, T* __restrict__ gd2) {
+    for (size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x; i < total; i += (size_t)gridDim.x * BLOCK) {
+        const size_t q = i / k;
+        const size_t b = q / n;
+        const int nb = rows_of(rows, (int)b, m);
+        T R = T(0), r;
+        for (int s = 0; s < k; ++s) {
+            interp_slot<T, I>(idx, d2, eps, q * k + s, nb, r);
+            R = R + r;
+        }
+        const int j = interp_slot<T, I>(idx, d2, eps, i, nb, r);
+        if (j < 0) {
+            if (gd2) gd2[i] = T(0);
+            continue;
+        }
+        const T w = interp_w<T>(r, R);
+        const T* Fj = f + (b * m + (size_t)j) * C;
+        T dot = T(0);
+        for (int c = 0; c < C; ++c) {
+            const T gc = g[q * C + c];
+            if (gd2) dot = interp_dot_add<T>(dot, gc, Fj[c], out[q * C + c]);
+            if (gf) unsafeAtomicAdd(gf + (b * m + (size_t)j) * C + c, w * gc);
+        }
+        if (gd2) gd2[i] = interp_gd2<T>(r, R, dot);
+    }
+}
+
+// ------------------------------------------------------------------ host side
+inline size_t tsize(int dtype) { return dtype == DICP_F32 ? 4 : 8; }
+
+// a * b * c < 2^62, without overflowing on the way (every factor >= 1 and < 2^31)
+inline bool fits62(size_t a, size_t b, size_t c) {
+    const size_t top = ((size_t)1 << 62) - 1;
+    return a <= top / b && a * b <= top / c;
+}
+
+int group_check(int dtype, int idx64, int N, int n, int m, int k, int C) {
+    if (bad_dtype(dtype)) return DICP_ERR_DTYPE;
+    if (idx64 != 0 && idx64 != 1) return DICP_ERR_ENUM;
+    if (N < 1 || n < 1 || m < 1 || k < 1 || k > GROUP_K_MAX || C < 1) return DICP_ERR_SHAPE;
+    // the largest element count, N n k C of the grouped tensor, and the bytes of the gradient table, 8 N m C, stay below 2^62
+    if (!fits62((size_t)N * n, (size_t)k, (size_t)C) || !fits62((size_t)N * m, 8, (size_t)C)) return DICP_ERR_SHAPE;
+    return 0;
+}
+inline bool misaligned(const void* p, size_t a) { return p && ((uintptr_t)p % a); }
+inline bool wide(int dtype, int C) { return (size_t)C * tsize(dtype) >= GROUP_WIDE_BYTES; }
+// rows of C elements are 16-byte segments from these bases on
+inline bool vec16(int dtype, int C, const void* a, const void* b) { return ((size_t)C * tsize(dtype)) % 16 == 0 && !(((uintptr_t)a | (uintptr_t)b) & 15); }
+
+template <typename T> struct VecOf { static constexpr int v = 16 / sizeof(T); };
+
+#define DICP_GROUP_DISPATCH(CALL) do { \
+        if (dtype == DICP_F32) { if (idx64) CALL(float, int64_t); else CALL(float, int32_t); } \
+        else                   { if (idx64) CALL(double, int64_t); else CALL(double, int32_t); } \
+    } while (0)
+
+}  // namespace
+
+int dicp_group_forward(int dtype, const void* features, const void* idx, int idx64, const int32_t* rows, const void* centers, int Cc,
+                       int N, int n, int m, int k, int C, void* out, void* stream) {
+    if (!features || !idx || !out || (Cc != 0 && !centers)) return DICP_ERR_NULL;
+    int rc = group_check(dtype, idx64, N, n, m, k, C);
+    if (rc) return rc;
+    if (Cc < 0 || Cc > C) return DICP_ERR_SHAPE;
+    const size_t ts = tsize(dtype);
+    if (misaligned(features, ts) || misaligned(out, ts) || misaligned(centers, ts) || misaligned(idx, idx64 ? 8 : 4) || misaligned(rows, 4)) return DICP_ERR_ALIGN;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t Q = (size_t)N * n, total = Q * k * C;
+    const bool w = wide(dtype, C), v = w && vec16(dtype, C, features, out);
+    begin_launch();
+#define DICP_GROUP_FWD(T, I) do { \
+        if (v)      group_fwd_wide_kernel<T, I, VecOf<T>::v><<<group_grid(Q, GW), BLOCK, 0, st>>>((const T*)features, (const I*)idx, rows, (const T*)centers, Cc, Q, n, m, k, C, (T*)out); \
+        else if (w) group_fwd_wide_kernel<T, I, 1><<<group_grid(Q, GW), BLOCK, 0, st>>>((const T*)features, (const I*)idx, rows, (const T*)centers, Cc, Q, n, m, k, C, (T*)out); \
+        else        group_fwd_narrow_kernel<T, I><<<group_grid(total, BLOCK), BLOCK, 0, st>>>((const T*)features, (const I*)idx, rows, (const T*)centers, Cc, total, n, m, k, C, (T*)out); \
+    } while (0)
+    DICP_GROUP_DISPATCH(DICP_GROUP_FWD);
+#undef DICP_GROUP_FWD
+    return launch_status();
+}
+
+int dicp_group_backward(int dtype, const void* grad_out, const void* idx, int idx64, const int32_t* rows, int Cc,
+                        int N, int n, int m, int k, int C, void* grad_features, void* grad_centers, void* stream) {
+    if (!grad_out || !idx || (!grad_features && !grad_centers)) return DICP_ERR_NULL;
+    int rc = group_check(dtype, idx64, N, n, m, k, C);
+    if (rc) return rc;
+    if (Cc < 0 || Cc > C || (grad_centers && Cc == 0)) return DICP_ERR_SHAPE;
+    const size_t ts = tsize(dtype);
+    if (misaligned(grad_out, ts) || misaligned(grad_features, ts) || misaligned(grad_centers, ts) || misaligned(idx, idx64 ? 8 : 4) || misaligned(rows, 4)) return DICP_ERR_ALIGN;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t Q = (size_t)N * n, total = Q * k * C, ctotal = Q * Cc;
+    if (grad_features && (rc = dicp_fill::zero(grad_features, (size_t)N * m * C * ts, st))) return rc;
+    begin_launch();
+#define DICP_GROUP_BWD(T, I) do { \
+        if (grad_features) group_bwd_kernel<T, I><<<group_grid(total, BLOCK), BLOCK, 0, st>>>((const T*)grad_out, (const I*)idx, rows, total, n, m, k, C, (T*)grad_features); \
+        if (grad_centers)  group_gcenters_kernel<T, I><<<group_grid(ctotal, BLOCK), BLOCK, 0, st>>>((const T*)grad_out, (const I*)idx, rows, Cc, ctotal, n, m, k, C, (T*)grad_centers); \
+    } while (0)
+    DICP_GROUP_DISPATCH(DICP_GROUP_BWD);
+#undef DICP_GROUP_BWD
+    return launch_status();
+}
+
+int dicp_interpolate_forward(int dtype, const void* features, const void* idx, int idx64, const int32_t* rows, const void* d2, double eps,
+                             int N, int n, int m, int k, int C, void* out, void* stream) {
+    if (!features || !idx || !d2 || !out) return DICP_ERR_NULL;
+    int rc = group_check(dtype, idx64, N, n, m, k, C);
+    if (rc) return rc;
+    if (!(eps > 0.0) || eps - eps != 0.0) return DICP_ERR_SHAPE;
+    const size_t ts = tsize(dtype);
+    if (misaligned(features, ts) || misaligned(out, ts) || misaligned(d2, ts) || misaligned(idx, idx64 ? 8 : 4) || misaligned(rows, 4)) return DICP_ERR_ALIGN;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t Q = (size_t)N * n, total = Q * C;
+    const bool w = wide(dtype, C), v = w && vec16(dtype, C, features, out);
+    begin_launch();
+#define DICP_INTERP_FWD(T, I) do { \
+        if (v)      interp_fwd_wide_kernel<T, I, VecOf<T>::v><<<group_grid(Q, GW), BLOCK, 0, st>>>((const T*)features, (const I*)idx, rows, (const T*)d2, (T)eps, Q, n, m, k, C, (T*)out); \
+        else if (w) interp_fwd_wide_kernel<T, I, 1><<<group_grid(Q, GW), BLOCK, 0, st>>>((const T*)features, (const I*)idx, rows, (const T*)d2, (T)eps, Q, n, m, k, C, (T*)out); \
+        else        interp_fwd_narrow_kernel<T, I><<<group_grid(total, BLOCK), BLOCK, 0, st>>>((const T*)features, (const I*)idx, rows, (const T*)d2, (T)eps, total, n, m, k, C, (T*)out); \
+    } while (0)
+    DICP_GROUP_DISPATCH(DICP_INTERP_FWD);
+#undef DICP_INTERP_FWD
+    return launch_status();
+}
+
+int dicp_interpolate_backward(int dtype, const void* grad_out, const void* features, const void* out, const void* idx, int idx64, const int32_t* rows,
+                              const void* d2, double eps, int N, int n, int m, int k, int C, void* grad_features, void* grad_d2, void* stream) {
+    if (!grad_out || !features || !out || !idx || !d2 || (!grad_features && !grad_d2)) return DICP_ERR_NULL;
+    int rc = group_check(dtype, idx64, N, n, m, k, C);
+    if (rc) return rc;
+    if (!(eps > 0.0) || eps - eps != 0.0) return DICP_ERR_SHAPE;
+    const size_t ts = tsize(dtype);
+    if (misaligned(grad_out, ts) || misaligned(features, ts) || misaligned(out, ts) || misaligned(d2, ts) || misaligned(grad_features, ts) || misaligned(grad_d2, ts)
+        || misaligned(idx, idx64 ? 8 : 4) || misaligned(rows, 4)) return DICP_ERR_ALIGN;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t Q = (size_t)N * n, total = Q * k;
+    if (grad_features && (rc = dicp_fill::zero(grad_features, (size_t)N * m * C * ts, st))) return rc;
+    const bool w = wide(dtype, C);
+    begin_launch();
+#define DICP_INTERP_BWD(T, I) do { \
+        if (w) interp_bwd_wide_kernel<T, I><<<group_grid(Q, GW), BLOCK, 0, st>>>((const T*)grad_out, (const T*)features, (const T*)out, (const I*)idx, rows, (const T*)d2, (T)eps, \
+                                                                                 Q, n, m, k, C, (T*)grad_features, (T*)grad_d2); \
+        else   interp_bwd_narrow_kernel<T, I><<<group_grid(total, BLOCK), BLOCK, 0, st>>>((const T*)grad_out, (const T*)features, (const T*)out, (const I*)idx, rows, (const T*)d2, (T)eps, \
+                                                                                        total, n, m, k, C, (T*)grad_features, (T*)grad_d2); \
+    } while (0)
+    DICP_GROUP_DISPATCH(DICP_INTERP_BWD);
+#undef DICP_INTERP_BWD
+    return launch_status();
+}

@@ -967,6 +967,30 @@ int dicp_knn_grid_query(int dtype, const void* x, int cx, int n, const uint64_t*
                         void* d2, int64_t* idx, void* workspace, size_t workspace_bytes, unsigned long long* visited, unsigned long long* passes,
                         void* stream);
 
+/* Neighbourhood features (dicp_amd/group.py: group_points, interpolate_features; the per-slot rules: csrc/dicp_group.h).
+ *   features (N,m,C) T, C >= 1; idx (N,n,k) int64 (idx64 = 1) or int32 (idx64 = 0), read as it is, 1 <= k <= 32; rows: optional (N) counts
+ *   of live feature rows.  Slot (b, i, s) is LIVE when 0 <= idx < rows[b] (m without rows): one unsigned compare, nothing is read out of
+ *   range whatever idx holds; every other slot is empty.  No workspace; nothing is read back; every launch is on `stream`.
+ *   grad_features (N,m,C) T is zero-filled by a kernel, then added to with float atomics (not bit-reproducible); the other gradients are
+ *   written once (bit-reproducible).
+ * dicp_group_forward: out (N,n,k,C) T = features[b, idx] on live slots (columns 0:Cc minus centers (N,n,Cc) T, one rounding; Cc = 0 and
+ *   centers = NULL: none), 0 on empty ones.
+ * dicp_group_backward: grad_features[b, idx] += grad_out[b, i, s] over the live slots; grad_centers (N,n,Cc) T = -(sum over the live slots
+ *   in slot order).  Either may be NULL.
+ * dicp_interpolate_forward: d2 (N,n,k) T; a slot is live when its index is live and its d2 is finite.  r = 1 / (d2 + (T)eps), R = sum r,
+ *   w = r / R, out (N,n,C) T = sum w features[b, idx], all in slot order; 0 without a live slot.  eps finite and > 0.
+ * dicp_interpolate_backward: out = the forward's result.  grad_features[b, idx] += w grad_out[b, i]; grad_d2 (N,n,k) T =
+ *   -(r^2 / R) sum_c grad_out[b, i, c] (features[b, idx, c] - out[b, i, c]) on live slots, 0 elsewhere.  Either may be NULL. */
+int dicp_group_forward(int dtype, const void* features, const void* idx, int idx64, const int32_t* rows, const void* centers, int Cc,
+                       int N, int n, int m, int k, int C, void* out, void* stream);
+int dicp_group_backward(int dtype, const void* grad_out, const void* idx, int idx64, const int32_t* rows, int Cc,
+                        int N, int n, int m, int k, int C, void* grad_features, void* grad_centers, void* stream);
+int dicp_interpolate_forward(int dtype, const void* features, const void* idx, int idx64, const int32_t* rows, const void* d2, double eps,
+                             int N, int n, int m, int k, int C, void* out, void* stream);
+int dicp_interpolate_backward(int dtype, const void* grad_out, const void* features, const void* out, const void* idx, int idx64,
+                              const int32_t* rows, const void* d2, double eps, int N, int n, int m, int k, int C,
+                              void* grad_features, void* grad_d2, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
