@@ -99,7 +99,8 @@ class ICP:
         trim_dist : None or a distance; loss_fn : None or {"name": "huber"|"cauchy"|"trim", "metric": x}
         dim : 3, or 2 to optimise rotation about z and translation in x,y only
         source_rows, target_rows (build-specific, optional): (N) row counts of a PADDED batch (N,n,3|6) / (N,m,3|6) -- ragged clouds without Python lists: rows
-                 past a cloud's count take no part (whatever they hold), as if the clouds had been given as a list of their own lengths.  A list of 256
+                 past a cloud's count take no part (whatever they hold; with Gumbel-softmax correspondences too: they enter no softmax and get
+                 zero gradient), as if the clouds had been given as a list of their own lengths.  A list of 256
                  clouds is 512 leaf tensors to autograd, ~8 ms of host time per call; the padded batch is one
         returns {"pc" (N,n,3), "T" (N,4,4), "costs" (N,K,1), "deltas" (N,K,6,1),
                  "weights" (N,K,n*r,1), "stats": {"converged","iterations","matched_ratio"}}
@@ -123,6 +124,11 @@ class ICP:
         source, target, T_init = (t.to(dev) for t in (source, target, T_init))
         w_pts = w_pts.to(dev) if w_pts is not None else None
         src_rows, tgt_rows = self._device_rows(rows, dev)
+        if self.nn.differentiable and self.nn.use_gumbel:
+            # soft correspondences of LISTS scan every pad row, as the reference does: its softmax runs over all the copies of the far point (a
+            # thousand copies carry a thousand times one copy's weight -- "first of equals" holds for an argmin only), and its zero source rows
+            # have weight 0.  Only caller-given counts of a padded batch (below) reach the soft loop.
+            src_rows = tgt_rows = None
         if source_rows is not None or target_rows is not None:
             if rows is not None:
                 raise ValueError("source_rows / target_rows describe a padded batch: not together with lists of clouds")

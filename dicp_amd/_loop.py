@@ -276,7 +276,7 @@ def _fwd_begin(ctx, source, target, T_init, w0, cfg):
     assert S.Kmax >= 1, "max_iterations must be at least 1"
     S.need_grad = any(ctx.needs_input_grad[:4])
     if cfg.stats_out is not None:       # the statistics describe THIS call (an earlier call's certificate counters must not outlive it)
-        for key in ("knn_pairs", "searched_again", "budgets", "bwd_live", "certs_off"):
+        for key in ("knn_pairs", "searched_again", "budgets", "bwd_live", "certs_off", "gumbel_seeds"):
             cfg.stats_out.pop(key, None)
     return S
 
@@ -473,6 +473,8 @@ def _fwd_loop_state(S):
         # in-kernel noise: one seed per iteration from torch's CPU generator (torch.manual_seed makes a call reproducible)
         S.seed_list = [int(v) & 0xFFFFFFFF for v in torch.randint(0, 2 ** 31 - 1, (Kmax,)).tolist()] if S.U_list is None else [0] * Kmax
         S.seeds = (ctypes.c_uint32 * Kmax)(*S.seed_list)
+        if cfg.stats_out is not None:       # read-only: the seeds this call's kernels (and its backward's) regenerate the noise from, one per iteration
+            cfg.stats_out["gumbel_seeds"] = tuple(S.seed_list)
         S.gum = _lib.GumbelLoop(U=ctypes.cast(S.U_arr, ctypes.c_void_p) if S.U_arr is not None else None, seeds=ctypes.cast(S.seeds, ctypes.c_void_p),
                                 eps=float(g_eps), tau=float(g_tau), ps_t=_p(S.ps_t), nbr=_p(S.nbr_hist), lse=_p(S.lse_hist))
         S.g_eps, S.g_tau = float(g_eps), float(g_tau)

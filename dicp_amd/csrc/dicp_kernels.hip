@@ -552,8 +552,15 @@ static int accumulate_bwd_go(int dtype, const dicp_weight_params* prm, const voi
     return launch_status();
 }
 
+// the three Gumbel kernels with optional per-cloud row counts of x and y (the soft loop's ragged batches); the public entries pass none
+static int gumbel_nn_go(int dtype, const void* x, const void* y, int c, const void* U, uint32_t seed, double eps, double tau,
+                        int N, int n, int m, void* out, void* lse, const int32_t* x_rows, const int32_t* y_rows, void* stream);
 int dicp_gumbel_nn(int dtype, const void* x, const void* y, int c, const void* U, uint32_t seed, double eps, double tau,
                    int N, int n, int m, void* out, void* lse, void* stream) {
+    return gumbel_nn_go(dtype, x, y, c, U, seed, eps, tau, N, n, m, out, lse, nullptr, nullptr, stream);
+}
+static int gumbel_nn_go(int dtype, const void* x, const void* y, int c, const void* U, uint32_t seed, double eps, double tau,
+                        int N, int n, int m, void* out, void* lse, const int32_t* x_rows, const int32_t* y_rows, void* stream) {
     if (!x || !y || !out || !lse) return DICP_ERR_NULL;
     if (bad_dtype(dtype)) return DICP_ERR_DTYPE;
     if (N <= 0 || n <= 0 || m <= 0 || (c != 3 && c != 6) || !(tau > 0.0)) return DICP_ERR_SHAPE;
@@ -561,7 +568,7 @@ int dicp_gumbel_nn(int dtype, const void* x, const void* y, int c, const void* U
     begin_launch();
     const int bpc = (n + BLOCK - 1) / BLOCK;
     const unsigned g = grid_for(N, bpc);
-#define DICP_GF(T, C) gumbel_fwd_kernel<T, C><<<g, BLOCK, 0, st>>>((const T*)x, (const T*)y, (const T*)U, seed, (T)eps, (T)(1.0 / tau), (T*)out, (T*)lse, N, n, m, bpc)
+#define DICP_GF(T, C) gumbel_fwd_kernel<T, C><<<g, BLOCK, 0, st>>>((const T*)x, (const T*)y, (const T*)U, seed, (T)eps, (T)(1.0 / tau), (T*)out, (T*)lse, N, n, m, bpc, x_rows, y_rows)
     if (dtype == DICP_F32) { if (c == 6) DICP_GF(float, 6); else DICP_GF(float, 3); }
     else                   { if (c == 6) DICP_GF(double, 6); else DICP_GF(double, 3); }
 #undef DICP_GF
@@ -569,13 +576,15 @@ int dicp_gumbel_nn(int dtype, const void* x, const void* y, int c, const void* U
 }
 
 static int gumbel_nn_bwd_go(int dtype, const void* x, const void* y, int c, const void* U, uint32_t seed, double eps, double tau,
-                            const void* out, const void* lse, const void* gout, int N, int n, int m, void* gx, void* gy, int add_gy, void* stream);
+                            const void* out, const void* lse, const void* gout, int N, int n, int m, void* gx, void* gy, int add_gy,
+                            const int32_t* x_rows, const int32_t* y_rows, void* stream);
 int dicp_gumbel_nn_bwd(int dtype, const void* x, const void* y, int c, const void* U, uint32_t seed, double eps, double tau,
                        const void* out, const void* lse, const void* gout, int N, int n, int m, void* gx, void* gy, void* stream) {
-    return gumbel_nn_bwd_go(dtype, x, y, c, U, seed, eps, tau, out, lse, gout, N, n, m, gx, gy, 0, stream);
+    return gumbel_nn_bwd_go(dtype, x, y, c, U, seed, eps, tau, out, lse, gout, N, n, m, gx, gy, 0, nullptr, nullptr, stream);
 }
 static int gumbel_nn_bwd_go(int dtype, const void* x, const void* y, int c, const void* U, uint32_t seed, double eps, double tau,
-                            const void* out, const void* lse, const void* gout, int N, int n, int m, void* gx, void* gy, int add_gy, void* stream) {
+                            const void* out, const void* lse, const void* gout, int N, int n, int m, void* gx, void* gy, int add_gy,
+                            const int32_t* x_rows, const int32_t* y_rows, void* stream) {
     if (!x || !y || !out || !lse || !gout || (!gx && !gy)) return DICP_ERR_NULL;
     if (bad_dtype(dtype)) return DICP_ERR_DTYPE;
     if (N <= 0 || n <= 0 || m <= 0 || (c != 3 && c != 6) || !(tau > 0.0)) return DICP_ERR_SHAPE;
@@ -583,8 +592,8 @@ static int gumbel_nn_bwd_go(int dtype, const void* x, const void* y, int c, cons
     begin_launch();
     const int bq = (n + BLOCK - 1) / BLOCK, bt = (m + BLOCK - 1) / BLOCK;
 #define DICP_GB(T, C) do { \
-        if (gx) gumbel_bwd_q_kernel<T, C><<<grid_for(N, bq), BLOCK, 0, st>>>((const T*)x, (const T*)y, (const T*)U, seed, (T)eps, (T)(1.0 / tau), (const T*)out, (const T*)lse, (const T*)gout, (T*)gx, N, n, m, bq); \
-        if (gy) gumbel_bwd_t_kernel<T, C><<<grid_for(N, bt), BLOCK, 0, st>>>((const T*)x, (const T*)y, (const T*)U, seed, (T)eps, (T)(1.0 / tau), (const T*)out, (const T*)lse, (const T*)gout, (T*)gy, N, n, m, bt, add_gy); } while (0)
+        if (gx) gumbel_bwd_q_kernel<T, C><<<grid_for(N, bq), BLOCK, 0, st>>>((const T*)x, (const T*)y, (const T*)U, seed, (T)eps, (T)(1.0 / tau), (const T*)out, (const T*)lse, (const T*)gout, (T*)gx, N, n, m, bq, x_rows, y_rows); \
+        if (gy) gumbel_bwd_t_kernel<T, C><<<grid_for(N, bt), BLOCK, 0, st>>>((const T*)x, (const T*)y, (const T*)U, seed, (T)eps, (T)(1.0 / tau), (const T*)out, (const T*)lse, (const T*)gout, (T*)gy, N, n, m, bt, add_gy, x_rows, y_rows); } while (0)
     if (dtype == DICP_F32) { if (c == 6) DICP_GB(float, 6); else DICP_GB(float, 3); }
     else                   { if (c == 6) DICP_GB(double, 6); else DICP_GB(double, 3); }
 #undef DICP_GB
@@ -865,7 +874,8 @@ static bool small_loop_eligible(int dtype, int kind, int knn_variant, int n, int
     return lds <= 48 * 1024 && (long)n * m_pad <= SMALL_PAIRS;
 }
 
-static int transform_points_bwd_go(int dtype, const void* src, const void* pose, const void* gout, void* gsrc, void* partials, int N, int n, int add, void* stream);
+static int transform_points_bwd_go(int dtype, const void* src, const void* pose, const void* gout, void* gsrc, void* partials, int N, int n, int add, void* stream,
+                                   const int32_t* src_rows = nullptr);
 // ------------------------------------------------------------------ whole-loop entry points
 // The iteration loop of ICP.dICP (ICP.py:131-260) behind ONE call: K x { kNN -> accumulate -> step } are
 // enqueued back to back on the stream with every piece of per-iteration state in caller-allocated buffers
@@ -984,13 +994,13 @@ int dicp_icp_forward(int dtype, const dicp_weight_params* prm, const dicp_loop_b
             char* nbr_k = (char*)G->nbr + (size_t)k * N * n * B->c * es;
             char* lse_k = (char*)G->lse + (size_t)k * N * n * es;
             rc = dicp_transform_points(dtype, B->src, pose_k, G->ps_t, N, n, stream);
-            if (!rc) rc = dicp_gumbel_nn(dtype, G->ps_t, B->tgt, B->c, G->U ? G->U[k] : nullptr, G->seeds ? G->seeds[k] : 0u, G->eps, G->tau, N, n, m, nbr_k, lse_k, stream);
+            if (!rc) rc = gumbel_nn_go(dtype, G->ps_t, B->tgt, B->c, G->U ? G->U[k] : nullptr, G->seeds ? G->seeds[k] : 0u, G->eps, G->tau, N, n, m, nbr_k, lse_k, B->src_rows, B->tgt_rows, stream);
             if (rc) return rc;
             if (B->events) {
                 if (hipEventRecord((hipEvent_t)B->events[6 * k + 1], st) != hipSuccess) return -(int)hipGetLastError();
                 set_launch_events((hipEvent_t)B->events[6 * k + 2], (hipEvent_t)B->events[6 * k + 3]);
             }
-            rc = accumulate_go(dtype, prm, B->src, nbr_k, B->c, nullptr, pose_k, B->w_init, alive_k, nullptr, N, n, n, B->partials, w_k, B->hist.w_stride, stream, nullptr, w_prev_k);
+            rc = accumulate_go(dtype, prm, B->src, nbr_k, B->c, nullptr, pose_k, B->w_init, alive_k, B->src_rows, N, n, n, B->partials, w_k, B->hist.w_stride, stream, nullptr, w_prev_k);
             set_launch_events(nullptr, nullptr);
             if (rc) return rc;
         } else {
@@ -1129,11 +1139,11 @@ int dicp_icp_backward(int dtype, const dicp_weight_params* prm, const dicp_loop_
             const char* nbr_k = (const char*)G->nbr + (size_t)k * N * n * B->c * es;
             const char* lse_k = (const char*)G->lse + (size_t)k * N * n * es;
             if (const int e = dicp_fill::zero(G->g_nbr, (size_t)N * n * B->c * es, st)) return e;
-            rc = accumulate_bwd_go(dtype, prm, B->src, nbr_k, B->c, nullptr, pose_k, B->w_init, alive_k, gs, gb, nullptr, N, n, n, gsrc, G->g_nbr, gw, bwd_partials, stream, B->bwd.skip);
+            rc = accumulate_bwd_go(dtype, prm, B->src, nbr_k, B->c, nullptr, pose_k, B->w_init, alive_k, gs, gb, B->src_rows, N, n, n, gsrc, G->g_nbr, gw, bwd_partials, stream, B->bwd.skip);
             if (!rc) rc = dicp_transform_points(dtype, B->src, pose_k, G->ps_t, N, n, stream);
             if (!rc) rc = gumbel_nn_bwd_go(dtype, G->ps_t, B->tgt, B->c, G->U ? G->U[k] : nullptr, G->seeds ? G->seeds[k] : 0u, G->eps, G->tau, nbr_k, lse_k, G->g_nbr,
-                                           N, n, m, G->g_ps, gtgt, 1, stream);
-            if (!rc) rc = transform_points_bwd_go(dtype, B->src, pose_k, G->g_ps, gsrc, bwd_partials, N, n, 1, stream);
+                                           N, n, m, G->g_ps, gtgt, 1, B->src_rows, B->tgt_rows, stream);
+            if (!rc) rc = transform_points_bwd_go(dtype, B->src, pose_k, G->g_ps, gsrc, bwd_partials, N, n, 1, stream, B->src_rows);
         } else if (B->hist.spos)    // windowed form: src / w_init / tgt are the SORTED copies, gsrc / gw accumulate in slot order, gtgt is the slab
             rc = accumulate_bwd_window_go(dtype, prm, B->src, B->tgt, B->c,
                                           (B->hist.spos_of && k >= B->hist.spos_of_from) ? MatchHist{B->hist.spos, B->hist.spos_of, k, N, n, (n + WAVE - 1) / WAVE} : plain_matches(B->hist.spos + (size_t)k * N * n, N, n),
@@ -1194,15 +1204,16 @@ int dicp_transform_points_bwd(int dtype, const void* src, const void* pose, cons
                               int N, int n, void* stream) {
     return transform_points_bwd_go(dtype, src, pose, gout, gsrc, partials, N, n, 0, stream);
 }
-static int transform_points_bwd_go(int dtype, const void* src, const void* pose, const void* gout, void* gsrc, void* partials, int N, int n, int add, void* stream) {
+static int transform_points_bwd_go(int dtype, const void* src, const void* pose, const void* gout, void* gsrc, void* partials, int N, int n, int add, void* stream,
+                                   const int32_t* src_rows) {
     if (!src || !pose || !gout || !partials) return DICP_ERR_NULL;
     if (bad_dtype(dtype)) return DICP_ERR_DTYPE;
     if (N <= 0 || n <= 0) return DICP_ERR_SHAPE;
     hipStream_t st = (hipStream_t)stream;
     begin_launch();
     const int bpc = dicp_accumulate_blocks(n);
-    if (dtype == DICP_F32) transform_bwd_kernel<float><<<grid_for(N, bpc), BLOCK, 0, st>>>((const float*)src, (const float*)pose, (const float*)gout, (float*)gsrc, (float*)partials, N, n, bpc, add);
-    else                   transform_bwd_kernel<double><<<grid_for(N, bpc), BLOCK, 0, st>>>((const double*)src, (const double*)pose, (const double*)gout, (double*)gsrc, (double*)partials, N, n, bpc, add);
+    if (dtype == DICP_F32) transform_bwd_kernel<float><<<grid_for(N, bpc), BLOCK, 0, st>>>((const float*)src, (const float*)pose, (const float*)gout, (float*)gsrc, (float*)partials, N, n, bpc, add, src_rows);
+    else                   transform_bwd_kernel<double><<<grid_for(N, bpc), BLOCK, 0, st>>>((const double*)src, (const double*)pose, (const double*)gout, (double*)gsrc, (double*)partials, N, n, bpc, add, src_rows);
     return launch_status();
 }
 

@@ -57,7 +57,7 @@ template <typename T> DICP_HD T wp_val(double v) {
 
 DICP_HD int tri(int i, int j) { return i * 6 - (i * (i - 1)) / 2 + (j - i); }   // i <= j
 
-// float32 on the device: the hardware's own one-instruction forms (v_sqrt_f32, v_rcp_f32, v_exp_f32: 1 ulp each), not the correctly rounded expansions --
+// float32 on the device: the hardware's own one-instruction forms (v_sqrt_f32, v_rcp_f32, v_exp_f32, v_log_f32: 1 ulp each; the last one through __logf in kernels_soft_svd.h), not the correctly rounded expansions --
 // a division is 10 vector instructions that way, tanhf ~40, sqrtf ~12, and the per-point functions below are instruction-bound: of the 430 vector instructions
 // the windowed backward spent per point, ~100 were these (profiles/r05_point_math.txt).  A weight or a gradient moves by parts in 1e7; north_star's float32
 // bar is 1e-4 / 1e-3, and every form of every kernel shares these functions, so results that are compared bit for bit (searches, certified iterations) still are.

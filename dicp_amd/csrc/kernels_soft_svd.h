@@ -8,6 +8,9 @@
 // from a counter-based hash of (seed, cloud, i, j), so the backward passes can regenerate it instead of
 // storing it.  Backward recomputes the probabilities from the saved log-sum-exp in two passes: one lane per
 // query (x-bar) and one lane per target (y-bar, no atomics).
+// Ragged batches (x_rows / y_rows, NULL: every row): a query past its cloud's count gets a zero row and zero gradient, a target past
+// its cloud's count enters no softmax and gets zero gradient -- whatever those rows hold.  The tiles start at j = 0 either way, so a
+// cloud of a padded batch is summed in exactly the order of a dense call on its own rows; U keeps the padded (N,n,m) layout.
 __device__ __forceinline__ unsigned mix32(unsigned v) {
     v ^= v >> 16; v *= 0x7feb352du; v ^= v >> 15; v *= 0x846ca68bu; v ^= v >> 16;
     return v;
@@ -34,12 +37,13 @@ constexpr int GUM_TILE = 512;
 template <typename T, int C>
 __global__ __launch_bounds__(BLOCK) void gumbel_fwd_kernel(const T* __restrict__ x, const T* __restrict__ y, const T* __restrict__ U,
                                                            unsigned seed, T eps, T inv_tau, T* __restrict__ out, T* __restrict__ lse,
-                                                           int N, int n, int m, int bpc) {
+                                                           int N, int n, int m, int bpc, const int32_t* __restrict__ x_rows, const int32_t* __restrict__ y_rows) {
     __shared__ T ty[GUM_TILE * C];
     int cloud, blk;
     if (!decode_block(bpc, N, cloud, blk)) return;
     const int tid = threadIdx.x, i = blk * BLOCK + tid;
-    const bool on = i < n;
+    const int mc = rows_of(y_rows, cloud, m);
+    const bool on = i < rows_of(x_rows, cloud, n);
     T xi[3] = {T(0), T(0), T(0)};
     if (on) { const T* xp = x + ((size_t)cloud * n + i) * 3; xi[0] = xp[0]; xi[1] = xp[1]; xi[2] = xp[2]; }
     const unsigned key = mix32(mix32(seed ^ ((unsigned)cloud * 0x9E3779B9u)) ^ ((unsigned)i * 0x85EBCA6Bu));
@@ -48,8 +52,8 @@ __global__ __launch_bounds__(BLOCK) void gumbel_fwd_kernel(const T* __restrict__
 #pragma unroll
     for (int k = 0; k < C; ++k) acc[k] = T(0);
     const T* __restrict__ yc = y + (size_t)cloud * m * C;
-    for (int base = 0; base < m; base += GUM_TILE) {
-        const int len = min(GUM_TILE, m - base);
+    for (int base = 0; base < mc; base += GUM_TILE) {
+        const int len = min(GUM_TILE, mc - base);
         for (int t = tid; t < len * C; t += BLOCK) ty[t] = yc[(size_t)base * C + t];
         __syncthreads();
         for (int j = 0; j < len; ++j) {
@@ -70,6 +74,11 @@ __global__ __launch_bounds__(BLOCK) void gumbel_fwd_kernel(const T* __restrict__
 #pragma unroll
         for (int k = 0; k < C; ++k) op[k] = acc[k] * invS;                        // probs @ y, nn.py:65-68
         lse[(size_t)cloud * n + i] = M + log_t(S);
+    } else if (i < n) {                                                            // a pad query of a ragged batch
+        T* op = out + ((size_t)cloud * n + i) * C;
+#pragma unroll
+        for (int k = 0; k < C; ++k) op[k] = T(0);
+        lse[(size_t)cloud * n + i] = T(0);
     }
 }
 
@@ -78,12 +87,13 @@ template <typename T, int C>
 __global__ __launch_bounds__(BLOCK) void gumbel_bwd_q_kernel(const T* __restrict__ x, const T* __restrict__ y, const T* __restrict__ U,
                                                              unsigned seed, T eps, T inv_tau, const T* __restrict__ out,
                                                              const T* __restrict__ lse, const T* __restrict__ gout, T* __restrict__ gx,
-                                                             int N, int n, int m, int bpc) {
+                                                             int N, int n, int m, int bpc, const int32_t* __restrict__ x_rows, const int32_t* __restrict__ y_rows) {
     __shared__ T ty[GUM_TILE * C];
     int cloud, blk;
     if (!decode_block(bpc, N, cloud, blk)) return;
     const int tid = threadIdx.x, i = blk * BLOCK + tid;
-    const bool on = i < n;
+    const int mc = rows_of(y_rows, cloud, m);
+    const bool on = i < rows_of(x_rows, cloud, n);
     const size_t q = (size_t)cloud * n + (on ? i : 0);
     T xi[3], go[C], D = T(0);
     xi[0] = x[q * 3]; xi[1] = x[q * 3 + 1]; xi[2] = x[q * 3 + 2];
@@ -93,8 +103,8 @@ __global__ __launch_bounds__(BLOCK) void gumbel_bwd_q_kernel(const T* __restrict
     const unsigned key = mix32(mix32(seed ^ ((unsigned)cloud * 0x9E3779B9u)) ^ ((unsigned)i * 0x85EBCA6Bu));
     T g[3] = {T(0), T(0), T(0)};
     const T* __restrict__ yc = y + (size_t)cloud * m * C;
-    for (int base = 0; base < m; base += GUM_TILE) {
-        const int len = min(GUM_TILE, m - base);
+    for (int base = 0; base < mc; base += GUM_TILE) {
+        const int len = min(GUM_TILE, mc - base);
         for (int t = tid; t < len * C; t += BLOCK) ty[t] = yc[(size_t)base * C + t];
         __syncthreads();
         for (int j = 0; j < len; ++j) {
@@ -112,6 +122,9 @@ __global__ __launch_bounds__(BLOCK) void gumbel_bwd_q_kernel(const T* __restrict
     if (on) {
         const T f = -T(2) * inv_tau;
         gx[q * 3] = f * g[0]; gx[q * 3 + 1] = f * g[1]; gx[q * 3 + 2] = f * g[2];
+    } else if (i < n) {                                                            // a pad query of a ragged batch
+        const size_t qp = (size_t)cloud * n + i;
+        gx[qp * 3] = T(0); gx[qp * 3 + 1] = T(0); gx[qp * 3 + 2] = T(0);
     }
 }
 
@@ -120,20 +133,22 @@ template <typename T, int C>
 __global__ __launch_bounds__(BLOCK) void gumbel_bwd_t_kernel(const T* __restrict__ x, const T* __restrict__ y, const T* __restrict__ U,
                                                              unsigned seed, T eps, T inv_tau, const T* __restrict__ out,
                                                              const T* __restrict__ lse, const T* __restrict__ gout, T* __restrict__ gy,
-                                                             int N, int n, int m, int bpc, int add /* 1: gy += (a loop's iterations add up) */) {
+                                                             int N, int n, int m, int bpc, int add /* 1: gy += (a loop's iterations add up) */,
+                                                             const int32_t* __restrict__ x_rows, const int32_t* __restrict__ y_rows) {
     constexpr int R = C + 5;
     __shared__ T tq[GUM_TILE * R];
     int cloud, blk;
     if (!decode_block(bpc, N, cloud, blk)) return;
     const int tid = threadIdx.x, j = blk * BLOCK + tid;
-    const bool on = j < m;
+    const int nc = rows_of(x_rows, cloud, n);
+    const bool on = j < rows_of(y_rows, cloud, m);
     const size_t tj = (size_t)cloud * m + (on ? j : 0);
     T yj[C], g[C];
 #pragma unroll
     for (int k = 0; k < C; ++k) { yj[k] = y[tj * C + k]; g[k] = T(0); }
     const unsigned kc = mix32(seed ^ ((unsigned)cloud * 0x9E3779B9u));
-    for (int base = 0; base < n; base += GUM_TILE) {
-        const int len = min(GUM_TILE, n - base);
+    for (int base = 0; base < nc; base += GUM_TILE) {
+        const int len = min(GUM_TILE, nc - base);
         for (int t = tid; t < len; t += BLOCK) {
             const size_t q = (size_t)cloud * n + base + t;
             T* r = tq + t * R;
@@ -162,6 +177,10 @@ __global__ __launch_bounds__(BLOCK) void gumbel_bwd_t_kernel(const T* __restrict
     if (on) {
 #pragma unroll
         for (int k = 0; k < C; ++k) gy[tj * C + k] = add ? gy[tj * C + k] + g[k] : g[k];
+    } else if (j < m && !add) {                                                    // a pad target of a ragged batch
+        const size_t tp = (size_t)cloud * m + j;
+#pragma unroll
+        for (int k = 0; k < C; ++k) gy[tp * C + k] = T(0);
     }
 }
 
@@ -358,7 +377,7 @@ __global__ __launch_bounds__(BLOCK) void transform_kernel(const T* __restrict__ 
 template <typename T>
 __global__ __launch_bounds__(BLOCK) void transform_bwd_kernel(const T* __restrict__ src, const T* __restrict__ pose, const T* __restrict__ gout,
                                                               T* __restrict__ gsrc, T* __restrict__ partials, int N, int n, int bpc,
-                                                              int add /* 1: gsrc and partials are added to */) {
+                                                              int add /* 1: gsrc and partials are added to */, const int32_t* __restrict__ src_rows /* NULL: every row */) {
     __shared__ T red[(BLOCK / WAVE) * NBWD_PAD];
     __shared__ T sums[NBWD_PAD];
     int cloud, blk;
@@ -368,7 +387,7 @@ __global__ __launch_bounds__(BLOCK) void transform_bwd_kernel(const T* __restric
     T acc[NBWD];
 #pragma unroll
     for (int k = 0; k < NBWD; ++k) acc[k] = T(0);
-    const int end = min(n, (blk + 1) * ACC_PTS);
+    const int end = min(rows_of(src_rows, cloud, n), (blk + 1) * ACC_PTS);
     for (int i = blk * ACC_PTS + threadIdx.x; i < end; i += BLOCK) {
         const size_t pt = ((size_t)cloud * n + i) * 3;
         const T p[3] = {src[pt], src[pt + 1], src[pt + 2]};
