@@ -21,6 +21,7 @@ PT2PT, PT2PL = 0, 1
 LOSS_NONE, LOSS_HUBER, LOSS_CAUCHY, LOSS_TRIM = 0, 1, 2, 3
 KNN_AUTO, KNN_VALU, KNN_MFMA, KNN_SWEEP, KNN_GUMBEL = 0, 1, 2, 3, 4
 FPS_AUTO, FPS_RESIDENT, FPS_STREAMED = 0, 1, 2
+POOL_SUM, POOL_MEAN, POOL_MAX = 0, 1, 2
 NACC_PAD, NBWD_PAD, KAB_SAVE = 32, 16, 40
 PAIR_SHARDS = 64      # DICP_PAIR_SHARDS
 ABI_VERSION = 11
@@ -268,6 +269,8 @@ _SIGNATURES = {
     "dicp_group_backward": ([i32, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp], ctypes.c_int),
     "dicp_interpolate_forward": ([i32, vp, vp, i32, vp, vp, f64, i32, i32, i32, i32, i32, vp, vp], ctypes.c_int),
     "dicp_interpolate_backward": ([i32, vp, vp, vp, vp, i32, vp, vp, f64, i32, i32, i32, i32, i32, vp, vp, vp], ctypes.c_int),
+    "dicp_pool_forward": ([i32, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp], ctypes.c_int),
+    "dicp_pool_backward": ([i32, vp, vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, i32, vp, vp], ctypes.c_int),
 }
 EXPORTS = tuple(_SIGNATURES)
 

@@ -1,4 +1,4 @@
-// Neighbourhood features (dicp_amd/group.py): gather and interpolate the rows of a feature table (N,m,C) through the (N,n,k) index
+// Neighbourhood features (dicp_amd/group.py): gather, interpolate and pool the rows of a feature table (N,m,C) through the (N,n,k) index
 // tensors of ball_query / knn_points, with their backward passes.  The per-slot rules are csrc/dicp_group.h's.
 //
 // All of it is memory traffic, so the kernels differ only in how threads are laid over it.  Two forms, chosen on the host by the row size:
@@ -13,6 +13,9 @@
 // loop), one element per lane: a wave adds 256 contiguous bytes of one row at C = 64 float32.  group_points' backward is flat in both
 // forms -- consecutive lanes are consecutive (slot, channel) elements, the same addresses a wave per query would add to.  g_centers and
 // g_d2 are written once per element without atomics; g_d2's channel sum is per-lane partial sums in channel order, then a butterfly.
+// pool_neighbors' wide forward does not give a query a whole wave: a query gets a GROUP of G lanes, G the smallest power of two that
+// holds the row's packs (8 <= G <= WAVE), and a wave works on WAVE / G queries at once -- at C = 64 float32 (16 packs of 16 bytes) four
+// queries per wave and every lane busy, where a wave per query keeps 16 of 64.  See pool_fwd_wide_kernel.
 // Every kernel is a grid-stride loop of at most GROUP_MAX_BLOCKS workgroups with 64-bit element counts.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -275,6 +278,169 @@ __global__ __launch_bounds__(BLOCK) void interp_bwd_narrow_kernel(const T* __res
     }
 }
 
+// ------------------------------------------------------------------ pool_neighbors
+constexpr int POOL_U = 4;                           // row loads a lane keeps in flight (slots per unrolled step); every G is a multiple of it
+
+// smallest power of two >= min(packs, WAVE), at least 8 (a wide row has at least 8 packs)
+inline int pool_lanes(int packs) {
+    int g = 8;
+    while (g < packs && g < WAVE) g <<= 1;
+    return g;
+}
+
+// G lanes per query, WAVE / G queries per wave, GW * WAVE / G per workgroup.  Lane gl of a group holds the row of slot s0 + gl; the group
+// reads the rows by shuffles of width G, POOL_U slots a step: their row loads are issued together, then folded in slot order.  Every loop
+// has wave-uniform trips and no lane leaves early (a query past Q holds -1 everywhere), so every shuffle's source lane is live.  A row of
+// more than G packs (only at G = WAVE) loops over v0; its k <= 32 indices are then one s0 step.  MAX: best / its row per channel of
+// the lane's pack, argmax stored as packs of V int32; otherwise the running sum, divided once by the count for the mean.
+template <typename T, typename I, int V, bool MAX>
+__global__ __launch_bounds__(BLOCK) void pool_fwd_wide_kernel(const T* __restrict__ f, const I* __restrict__ idx, const int32_t* __restrict__ rows, size_t Q, int n, int m, int k, int C,
+                                                              int G, int mean, T* __restrict__ out, int32_t* __restrict__ amax, int32_t* __restrict__ counts) {
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int gl = lane & (G - 1);
+    const int QW = WAVE / G, VR = C / V;
+    const size_t per_block = (size_t)GW * QW;
+    const size_t q_in = (size_t)(threadIdx.x / WAVE) * QW + lane / G;
+    for (size_t q0 = (size_t)blockIdx.x * per_block; q0 < Q; q0 += (size_t)gridDim.x * per_block) {
+        const size_t q = q0 + q_in;
+        const bool valid = q < Q;
+        const size_t b = valid ? q / n : 0;
+        const int nb = valid ? rows_of(rows, (int)b, m) : 0;
+        const T* F = f + b * m * C;
+        for (int v0 = 0; v0 < VR; v0 += G) {
+            const bool on = valid && v0 + gl < VR;
+            const int c = (v0 + gl) * V;
+            Pack<T, V> acc;
+            Pack<int32_t, V> arg;
+#pragma unroll
+            for (int e = 0; e < V; ++e) { acc.v[e] = T(0); arg.v[e] = -1; }
+            int cnt = 0;
+            for (int s0 = 0; s0 < k; s0 += G) {
+                const int jr = (valid && s0 + gl < k) ? group_row(idx[q * k + s0 + gl], nb) : -1;
+                const int lim = min(G, k - s0);
+                for (int t0 = 0; t0 < lim; t0 += POOL_U) {
+                    int j[POOL_U];
+                    Pack<T, V> x[POOL_U];
+#pragma unroll
+                    for (int u = 0; u < POOL_U; ++u) j[u] = __shfl(jr, t0 + u, G);     // (a lane past lim holds -1)
+#pragma unroll
+                    for (int u = 0; u < POOL_U; ++u) {
+#pragma unroll
+                        for (int e = 0; e < V; ++e) x[u].v[e] = T(0);
+                        if (on && j[u] >= 0) x[u] = pack_load<T, V>(F + (size_t)j[u] * C + c);
+                    }
+#pragma unroll
+                    for (int u = 0; u < POOL_U; ++u) {
+                        if (j[u] < 0) continue;
+                        ++cnt;
+#pragma unroll
+                        for (int e = 0; e < V; ++e) {
+                            if (MAX) pool_max_step<T>(x[u].v[e], j[u], acc.v[e], arg.v[e]);
+                            else acc.v[e] = pool_sum_step<T>(acc.v[e], x[u].v[e]);
+                        }
+                    }
+                }
+            }
+            if (on) {
+                if (!MAX && mean) {
+#pragma unroll
+                    for (int e = 0; e < V; ++e) acc.v[e] = pool_mean<T>(acc.v[e], cnt);
+                }
+                pack_store<T, V>(out + q * C + c, acc);
+                if (MAX) pack_store<int32_t, V>(amax + q * C + c, arg);
+            }
+            if (valid && v0 == 0 && gl == 0) counts[q] = cnt;
+        }
+    }
+}
+
+// one thread per (query, channel): out and argmax are stored contiguously along the flattened index.  The threads of a query (and, at
+// C = 1, the 64 lanes of a wave) would read the query's k indices at a pitch of k elements, 64 cache lines an instruction; instead the
+// workgroup turns the indices of its queries -- one contiguous range -- into row numbers (-1: empty) in LDS with coalesced loads, each
+// index read once, at an odd pitch so that lanes of different queries are on different banks.  The slot loop is unrolled by POOL_U like
+// the wide form's: the gathers of a step are issued before the first is folded.
+template <typename T, typename I, bool MAX>
+__global__ __launch_bounds__(BLOCK) void pool_fwd_narrow_kernel(const T* __restrict__ f, const I* __restrict__ idx, const int32_t* __restrict__ rows, size_t total, int n, int m, int k, int C,
+                                                                int mean, T* __restrict__ out, int32_t* __restrict__ amax, int32_t* __restrict__ counts) {
+    extern __shared__ int pool_rows[];                      // [(BLOCK - 1) / C + 2 queries][k | 1]
+    const int pitch = k | 1;
+    for (size_t i0 = (size_t)blockIdx.x * BLOCK; i0 < total; i0 += (size_t)gridDim.x * BLOCK) {        // (workgroup-uniform: the barriers)
+        const size_t q_lo = i0 / C;
+        const size_t last = (i0 + BLOCK < total ? i0 + BLOCK : total) - 1;
+        const int nq = (int)(last / C - q_lo) + 1;          // <= (BLOCK - 1) / C + 2
+        for (int t = threadIdx.x; t < nq * k; t += BLOCK) {
+            const int ql = t / k, s = t - ql * k;
+            const size_t q = q_lo + ql;
+            pool_rows[ql * pitch + s] = group_row(idx[q * k + s], rows_of(rows, (int)(q / n), m));
+        }
+        __syncthreads();
+        const size_t i = i0 + threadIdx.x;
+        if (i < total) {
+            const size_t q = i / C;
+            const int c = (int)(i - q * C);
+            const size_t b = q / n;
+            const int* jr = pool_rows + (int)(q - q_lo) * pitch;
+            const T* F = f + b * m * C + c;
+            T acc = T(0);
+            int arg = -1, cnt = 0;
+            for (int s0 = 0; s0 < k; s0 += POOL_U) {
+                int j[POOL_U];
+                T x[POOL_U];
+#pragma unroll
+                for (int u = 0; u < POOL_U; ++u) j[u] = s0 + u < k ? jr[s0 + u] : -1;
+#pragma unroll
+                for (int u = 0; u < POOL_U; ++u) {
+                    x[u] = T(0);
+                    if (j[u] >= 0) x[u] = F[(size_t)j[u] * C];
+                }
+#pragma unroll
+                for (int u = 0; u < POOL_U; ++u) {
+                    if (j[u] < 0) continue;
+                    ++cnt;
+                    if (MAX) pool_max_step<T>(x[u], j[u], acc, arg);
+                    else acc = pool_sum_step<T>(acc, x[u]);
+                }
+            }
+            if (!MAX && mean) acc = pool_mean<T>(acc, cnt);
+            out[i] = acc;
+            if (MAX) amax[i] = arg;
+            if (c == 0) counts[q] = cnt;
+        }
+        __syncthreads();                                    // (the next range overwrites the rows)
+    }
+}
+
+// g_features (zeroed) [argmax[q, c], c] += g[q, c]: flat over (query, channel); -1 (no live slot) adds nothing.  The row goes through
+// group_row again, so that nothing is added out of range whatever the argmax buffer holds
+template <typename T>
+__global__ __launch_bounds__(BLOCK) void pool_bwd_max_kernel(const T* __restrict__ g, const int32_t* __restrict__ amax, const int32_t* __restrict__ rows, size_t total, int n, int m, int C,
+                                                             T* __restrict__ gf) {
+    for (size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x; i < total; i += (size_t)gridDim.x * BLOCK) {
+        const size_t q = i / C;
+        const int c = (int)(i - q * C);
+        const size_t b = q / n;
+        const int j = group_row(amax[i], rows_of(rows, (int)b, m));
+        if (j >= 0) unsafeAtomicAdd(gf + (b * m + (size_t)j) * C + c, g[i]);
+    }
+}
+
+// g_features (zeroed) += g[q, :] (divided by the count: counts != NULL, the mean) over the live slots: flat over (query, slot, channel) as
+// group_bwd_kernel, the cotangent read per query instead of per slot
+template <typename T, typename I>
+__global__ __launch_bounds__(BLOCK) void pool_bwd_sum_kernel(const T* __restrict__ g, const I* __restrict__ idx, const int32_t* __restrict__ rows, const int32_t* __restrict__ counts,
+                                                             size_t total, int n, int m, int k, int C, T* __restrict__ gf) {
+    for (size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x; i < total; i += (size_t)gridDim.x * BLOCK) {
+        const size_t slot = i / C;
+        const int c = (int)(i - slot * C);
+        const size_t q = slot / k, b = q / n;
+        const int j = group_row(idx[slot], rows_of(rows, (int)b, m));
+        if (j < 0) continue;
+        T v = g[q * C + c];
+        if (counts) v = pool_mean_grad<T>(v, counts[q]);
+        unsafeAtomicAdd(gf + (b * m + (size_t)j) * C + c, v);
+    }
+}
+
 // ------------------------------------------------------------------ host side
 inline size_t tsize(int dtype) { return dtype == DICP_F32 ? 4 : 8; }
 
@@ -393,5 +559,59 @@ int dicp_interpolate_backward(int dtype, const void* grad_out, const void* featu
     } while (0)
     DICP_GROUP_DISPATCH(DICP_INTERP_BWD);
 #undef DICP_INTERP_BWD
+    return launch_status();
+}
+
+int dicp_pool_forward(int dtype, const void* features, const void* idx, int idx64, const int32_t* rows, int reduce,
+                      int N, int n, int m, int k, int C, void* out, int32_t* argmax, int32_t* counts, void* stream) {
+    if (!features || !idx || !out || !counts) return DICP_ERR_NULL;
+    if (reduce != DICP_POOL_SUM && reduce != DICP_POOL_MEAN && reduce != DICP_POOL_MAX) return DICP_ERR_ENUM;
+    if (reduce == DICP_POOL_MAX && !argmax) return DICP_ERR_NULL;
+    if (reduce != DICP_POOL_MAX && argmax) return DICP_ERR_ENUM;
+    int rc = group_check(dtype, idx64, N, n, m, k, C);
+    if (rc) return rc;
+    const size_t ts = tsize(dtype);
+    if (misaligned(features, ts) || misaligned(out, ts) || misaligned(argmax, 4) || misaligned(counts, 4) || misaligned(idx, idx64 ? 8 : 4) || misaligned(rows, 4)) return DICP_ERR_ALIGN;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t Q = (size_t)N * n, total = Q * C;
+    const bool w = wide(dtype, C), v = w && vec16(dtype, C, features, out) && !((uintptr_t)argmax & 15);
+    const int G = pool_lanes(v ? C / (int)(16 / ts) : C), per_block = GW * (WAVE / G), mean = reduce == DICP_POOL_MEAN;
+    const size_t narrow_lds = (size_t)((BLOCK - 1) / C + 2) * (k | 1) * sizeof(int);     // at most 257 x 33 x 4 bytes
+    begin_launch();
+#define DICP_POOL_FWD_R(T, I, MAX) do { \
+        if (v)      pool_fwd_wide_kernel<T, I, VecOf<T>::v, MAX><<<group_grid(Q, per_block), BLOCK, 0, st>>>((const T*)features, (const I*)idx, rows, Q, n, m, k, C, G, mean, (T*)out, argmax, counts); \
+        else if (w) pool_fwd_wide_kernel<T, I, 1, MAX><<<group_grid(Q, per_block), BLOCK, 0, st>>>((const T*)features, (const I*)idx, rows, Q, n, m, k, C, G, mean, (T*)out, argmax, counts); \
+        else        pool_fwd_narrow_kernel<T, I, MAX><<<group_grid(total, BLOCK), BLOCK, narrow_lds, st>>>((const T*)features, (const I*)idx, rows, total, n, m, k, C, mean, (T*)out, argmax, counts); \
+    } while (0)
+#define DICP_POOL_FWD(T, I) do { if (reduce == DICP_POOL_MAX) DICP_POOL_FWD_R(T, I, true); else DICP_POOL_FWD_R(T, I, false); } while (0)
+    DICP_GROUP_DISPATCH(DICP_POOL_FWD);
+#undef DICP_POOL_FWD
+#undef DICP_POOL_FWD_R
+    return launch_status();
+}
+
+int dicp_pool_backward(int dtype, const void* grad_out, const void* idx, int idx64, const int32_t* rows, int reduce,
+                       const int32_t* argmax, const int32_t* counts, int N, int n, int m, int k, int C, void* grad_features, void* stream) {
+    if (!grad_out || !idx || !grad_features) return DICP_ERR_NULL;
+    if (reduce != DICP_POOL_SUM && reduce != DICP_POOL_MEAN && reduce != DICP_POOL_MAX) return DICP_ERR_ENUM;
+    if ((reduce == DICP_POOL_MAX && !argmax) || (reduce == DICP_POOL_MEAN && !counts)) return DICP_ERR_NULL;
+    if (reduce != DICP_POOL_MAX && argmax) return DICP_ERR_ENUM;
+    int rc = group_check(dtype, idx64, N, n, m, k, C);
+    if (rc) return rc;
+    const size_t ts = tsize(dtype);
+    if (misaligned(grad_out, ts) || misaligned(grad_features, ts) || misaligned(argmax, 4) || misaligned(counts, 4) || misaligned(idx, idx64 ? 8 : 4) || misaligned(rows, 4)) return DICP_ERR_ALIGN;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t Q = (size_t)N * n, qc = Q * C, total = qc * k;
+    if ((rc = dicp_fill::zero(grad_features, (size_t)N * m * C * ts, st))) return rc;
+    const int32_t* cnt = reduce == DICP_POOL_MEAN ? counts : nullptr;
+    begin_launch();
+    if (reduce == DICP_POOL_MAX) {
+        if (dtype == DICP_F32) pool_bwd_max_kernel<float><<<group_grid(qc, BLOCK), BLOCK, 0, st>>>((const float*)grad_out, argmax, rows, qc, n, m, C, (float*)grad_features);
+        else                   pool_bwd_max_kernel<double><<<group_grid(qc, BLOCK), BLOCK, 0, st>>>((const double*)grad_out, argmax, rows, qc, n, m, C, (double*)grad_features);
+    } else {
+#define DICP_POOL_BWD(T, I) pool_bwd_sum_kernel<T, I><<<group_grid(total, BLOCK), BLOCK, 0, st>>>((const T*)grad_out, (const I*)idx, rows, cnt, total, n, m, k, C, (T*)grad_features)
+        DICP_GROUP_DISPATCH(DICP_POOL_BWD);
+#undef DICP_POOL_BWD
+    }
     return launch_status();
 }

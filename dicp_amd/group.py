@@ -1,12 +1,13 @@
-"""Differentiable neighbourhood features: gather and interpolate a feature table through the index tensors of the neighbour operators.
+"""Differentiable neighbourhood features: gather, pool and interpolate a feature table through the index tensors of the neighbour operators.
 
-The feature half of the point-cloud front end, on the GPU (libdicp_hip.so: dicp_group_* / dicp_interpolate_*; the per-slot rules:
-csrc/dicp_group.h).  ball_query and knn_points return (..., n, k) indices whose empty slots hold -1; these functions read them as they
+The feature half of the point-cloud front end, on the GPU (libdicp_hip.so: dicp_group_* / dicp_pool_* / dicp_interpolate_*; the per-slot
+rules: csrc/dicp_group.h).  ball_query and knn_points return (..., n, k) indices whose empty slots hold -1; these functions read them as they
 are -- no clamp, no expanded index, no mask, no read-back:
 
-    from dicp_amd.group import group_points, interpolate_features
+    from dicp_amd.group import group_points, pool_neighbors, interpolate_features
     d2, idx = ball_query(centres, cloud, 0.5, k=16, x_rows=crows, y_rows=rows)
     grouped = group_points(table, idx, rows=rows, centers=centres)        # (N, n, 16, C): table[idx] with columns 0:3 relative to the centre
+    pooled = pool_neighbors(per_point, idx, "max", rows=rows)             # (N, n, C): the maximum over each neighbourhood, nothing grouped
     d2, idx3 = knn_points(points, centres, k=3, y_rows=crows)
     w = interpolate_features(w_centres, idx3, d2, rows=crows)              # (N, n_points, 1): PointNet++'s feature propagation
 
@@ -15,8 +16,9 @@ kernel, so nothing is read out of range whatever idx holds and nothing is checke
 negative value, anything at or past the row count.  Query rows past their cloud's count need no argument: the neighbour operators give
 them -1 in every slot.
 
-Nothing is read back from the device and every launch is on the current stream.  A call inside a captured graph (torch.cuda.graph) has
-not been verified and is not claimed to work.
+Nothing is read back from the device and every launch is on the current stream, the zero fill of a gradient table included (a kernel,
+not a memset node).  With device tensors and device rows (or none) a call, forward and backward, can be captured in a graph
+(torch.cuda.graph) and replayed on new data in the same buffers: tests/test_gpu_group_graph.py does so for the three operators.
 """
 import math
 
@@ -102,6 +104,41 @@ class _Interpolate(torch.autograd.Function):
         return gf, None, gd, None, None
 
 
+class _Pool(torch.autograd.Function):
+    """(features (N,m,C), idx (N,n,k), rows, reduce) -> out (N,n,C), argmax (N,n,C) int32 (max; otherwise an empty tensor), counts (N,n) int32:
+    one library call per direction."""
+
+    @staticmethod
+    def forward(ctx, f, idx, rows, reduce):
+        N, n, m, k, C = _dims(f, idx)
+        out = torch.empty((N, n, C), dtype=f.dtype, device=f.device)
+        amax = torch.empty((N, n, C) if reduce == _lib.POOL_MAX else (0,), dtype=torch.int32, device=f.device)
+        counts = torch.empty((N, n), dtype=torch.int32, device=f.device)
+        with _on(f.device):
+            _lib.check(_lib.load().dicp_pool_forward(_DT[f.dtype], _p(f), _p(idx), _i64(idx), _p(rows), reduce, N, n, m, k, C, _p(out),
+                                                     _p(amax) if reduce == _lib.POOL_MAX else None, _p(counts), _stream()), "dicp_pool_forward")
+        ctx.save_for_backward(idx, rows, amax, counts)
+        ctx.dims, ctx.reduce = (N, n, m, k, C), reduce
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(amax, counts)
+        return out, amax, counts
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g, _ga, _gc):
+        if g is None or not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        idx, rows, amax, counts = ctx.saved_tensors
+        N, n, m, k, C = ctx.dims
+        g = g.contiguous()
+        gf = torch.empty((N, m, C), dtype=g.dtype, device=g.device)
+        with _on(g.device):
+            _lib.check(_lib.load().dicp_pool_backward(_DT[g.dtype], _p(g), _p(idx), _i64(idx), _p(rows), ctx.reduce,
+                                                      _p(amax) if ctx.reduce == _lib.POOL_MAX else None, _p(counts), N, n, m, k, C, _p(gf), _stream()),
+                       "dicp_pool_backward")
+        return gf, None, None, None
+
+
 def _front(features, idx, rows, what):
     """The checks the two functions share (no device is touched) -> (form, features batch, rows, idx batch, lengths of idx's list)"""
     form, fb, rows, _ = _clouds.check(features, rows, what, "features", "rows", min_cols=1)
@@ -149,7 +186,7 @@ def group_points(features, idx, rows=None, centers=None):
     cotangent arrives there, NaN and inf included.
 
     Nothing is read back and every launch is on the current stream: a call on device tensors (device or no rows) is kernels only; a list
-    or CPU rows add a host-to-device copy.  Capture in a graph is not verified (see the module's docstring).
+    or CPU rows add a host-to-device copy.  Capture in a graph: see the module's docstring.
     """
     what = "group_points"
     form, fb, rows, ib, lens = _front(features, idx, rows, what)
@@ -160,6 +197,56 @@ def group_points(features, idx, rows=None, centers=None):
     on_cpu, f_d, rows_d = _clouds.place(fb, rows)
     out = _Group.apply(f_d, ib.to(f_d.device).contiguous(), rows_d, cb.to(f_d.device).contiguous() if cb is not None else None)
     return _clouds.restore(form, on_cpu, ib.shape[1], lens, [(ROW, out)])[0]
+
+
+_REDUCE = {"sum": _lib.POOL_SUM, "mean": _lib.POOL_MEAN, "max": _lib.POOL_MAX}
+
+
+def pool_neighbors(features, idx, reduce="max", rows=None, return_argmax=False, return_counts=False):
+    """The maximum, mean or sum of the feature rows that idx names, per query and channel, over the k slots: group_points followed by a
+    reduction over the slots, without the (N, n, k, C) tensor in between (nor its n k C gradient atomics: n C for the maximum).
+
+    features, idx, rows: as group_points -- one table (m, C) with idx (n, k), a padded batch with rows, or lists; float32 or float64;
+        int64 or int32 indices read as they are, 1 <= k <= 32; C >= 1.  A slot is live when 0 <= idx < rows[b] (m, m_b).
+    reduce: "max", "mean" or "sum".
+    return_argmax: also return argmax (..., n, C) int32 (only with "max").  return_counts: also return counts (..., n) int32, the number
+        of live slots of each query.
+
+    Definition, per query i and channel c, every operation in the features' dtype T, over the live slots in slot order:
+      "sum":  acc = 0, then acc = acc + features[idx_s, c] for each live slot: plain additions, bit-reproducible.
+      "mean": that sum, then one division by T(count); within (k + 2) u sum_s |features[idx_s, c]| / count of the exact mean, u the unit
+              roundoff of T.
+      "max":  best starts at the first live slot's value; a later value v replaces it when v > best -- on ties the lowest slot wins, and
+              +0 and -0 tie -- or when v is NaN and best is not: a NaN propagates as in torch.max, and the first NaN's slot is the
+              argmax.  argmax[i, c] is the TABLE ROW idx[i, s] of the winning slot, not s.  +-inf are ordinary values.  Exact.
+      A query without a live slot gives out = 0, argmax = -1, counts = 0; so do the rows of a list's or a padded batch's queries past
+      their cloud's count (the neighbour operators give them -1 in every slot).
+
+    There is no centers argument: rounding to nearest is monotone, so max_s(f_s - centre) = max_s(f_s) - centre exactly -- subtract the
+    centre's row from the pooled result.  (For the mean and the sum the two orders differ by roundings; group_points(centers=) is there.)
+
+    Returns out (n, C), (N, n, C) or a list of (n_b, C); with return_argmax and / or return_counts a tuple (out, argmax, counts) of the
+    ones asked for, in this order.
+
+    Gradients: "max": features[argmax[i, c], c] receives g[i, c]; "sum": every live slot's row receives g[i, :]; "mean": every live
+    slot's row receives g[i, c] / T(count), one rounding.  All three add with float atomics, as group_points (the last bits can differ
+    from run to run); rows nobody points at get exactly 0.  A query without a live slot contributes nothing whatever cotangent arrives
+    there, NaN and inf included.  argmax and counts carry no gradient.
+
+    Nothing is read back, every launch is on the current stream, and nothing is checked on the host beyond shapes; capture in a graph:
+    see the module's docstring.
+    """
+    what = "pool_neighbors"
+    if not isinstance(reduce, str) or reduce not in _REDUCE:
+        raise ValueError("%s: reduce must be 'max', 'mean' or 'sum', got %r" % (what, reduce))
+    if return_argmax and reduce != "max":
+        raise ValueError("%s: return_argmax needs reduce='max', got %r" % (what, reduce))
+    form, fb, rows, ib, lens = _front(features, idx, rows, what)
+    on_cpu, f_d, rows_d = _clouds.place(fb, rows)
+    out, amax, counts = _Pool.apply(f_d, ib.to(f_d.device).contiguous(), rows_d, _REDUCE[reduce])
+    outs = [(ROW, out)] + ([(ROW, amax)] if return_argmax else []) + ([(ROW, counts)] if return_counts else [])
+    res = _clouds.restore(form, on_cpu, ib.shape[1], lens, outs)
+    return res if len(res) > 1 else res[0]
 
 
 def interpolate_features(features, idx, d2, eps=1e-8, rows=None):

@@ -967,7 +967,7 @@ int dicp_knn_grid_query(int dtype, const void* x, int cx, int n, const uint64_t*
                         void* d2, int64_t* idx, void* workspace, size_t workspace_bytes, unsigned long long* visited, unsigned long long* passes,
                         void* stream);
 
-/* Neighbourhood features (dicp_amd/group.py: group_points, interpolate_features; the per-slot rules: csrc/dicp_group.h).
+/* Neighbourhood features (dicp_amd/group.py: group_points, interpolate_features, pool_neighbors; the per-slot rules: csrc/dicp_group.h).
  *   features (N,m,C) T, C >= 1; idx (N,n,k) int64 (idx64 = 1) or int32 (idx64 = 0), read as it is, 1 <= k <= 32; rows: optional (N) counts
  *   of live feature rows.  Slot (b, i, s) is LIVE when 0 <= idx < rows[b] (m without rows): one unsigned compare, nothing is read out of
  *   range whatever idx holds; every other slot is empty.  No workspace; nothing is read back; every launch is on `stream`.
@@ -980,7 +980,18 @@ int dicp_knn_grid_query(int dtype, const void* x, int cx, int n, const uint64_t*
  * dicp_interpolate_forward: d2 (N,n,k) T; a slot is live when its index is live and its d2 is finite.  r = 1 / (d2 + (T)eps), R = sum r,
  *   w = r / R, out (N,n,C) T = sum w features[b, idx], all in slot order; 0 without a live slot.  eps finite and > 0.
  * dicp_interpolate_backward: out = the forward's result.  grad_features[b, idx] += w grad_out[b, i]; grad_d2 (N,n,k) T =
- *   -(r^2 / R) sum_c grad_out[b, i, c] (features[b, idx, c] - out[b, i, c]) on live slots, 0 elsewhere.  Either may be NULL. */
+ *   -(r^2 / R) sum_c grad_out[b, i, c] (features[b, idx, c] - out[b, i, c]) on live slots, 0 elsewhere.  Either may be NULL.
+ * dicp_pool_forward: out (N,n,C) T = the reduction of features[b, idx[b, i, s], c] over the live slots s in slot order, without the
+ *   (N,n,k,C) tensor.  DICP_POOL_SUM: acc = 0, acc = acc + value (plain additions: bit-reproducible).  DICP_POOL_MEAN: the sum, then one
+ *   division by T(count).  DICP_POOL_MAX: the first live slot's value, replaced by a later v when v > best (ties keep the lowest slot; +0
+ *   and -0 tie) or when v is NaN and best is not; argmax (N,n,C) int32 = the ROW idx of the winning slot (not the slot number).  A query
+ *   without a live slot gives out = 0, argmax = -1.  counts (N,n) int32 = the live slots of each query, always written.  argmax is
+ *   required for MAX (DICP_ERR_NULL without) and must be NULL otherwise (DICP_ERR_ENUM: the buffer does not go with the reduce).
+ * dicp_pool_backward: MAX: grad_features[b, argmax[b, i, c], c] += grad_out[b, i, c] (argmax >= 0; it is bounds-checked like an index);
+ *   SUM: every live slot's row += grad_out[b, i, :]; MEAN: += grad_out[b, i, c] / T(counts[b, i]) (counts as the forward wrote them;
+ *   required for MEAN, DICP_ERR_NULL without).  argmax as for the forward.  A query without a live slot adds nothing whatever its
+ *   cotangent holds. */
+enum { DICP_POOL_SUM = 0, DICP_POOL_MEAN = 1, DICP_POOL_MAX = 2 };
 int dicp_group_forward(int dtype, const void* features, const void* idx, int idx64, const int32_t* rows, const void* centers, int Cc,
                        int N, int n, int m, int k, int C, void* out, void* stream);
 int dicp_group_backward(int dtype, const void* grad_out, const void* idx, int idx64, const int32_t* rows, int Cc,
@@ -990,6 +1001,10 @@ int dicp_interpolate_forward(int dtype, const void* features, const void* idx, i
 int dicp_interpolate_backward(int dtype, const void* grad_out, const void* features, const void* out, const void* idx, int idx64,
                               const int32_t* rows, const void* d2, double eps, int N, int n, int m, int k, int C,
                               void* grad_features, void* grad_d2, void* stream);
+int dicp_pool_forward(int dtype, const void* features, const void* idx, int idx64, const int32_t* rows, int reduce,
+                      int N, int n, int m, int k, int C, void* out, int32_t* argmax, int32_t* counts, void* stream);
+int dicp_pool_backward(int dtype, const void* grad_out, const void* idx, int idx64, const int32_t* rows, int reduce,
+                       const int32_t* argmax, const int32_t* counts, int N, int n, int m, int k, int C, void* grad_features, void* stream);
 
 #ifdef __cplusplus
 }
