@@ -9,6 +9,8 @@ import torch
 from ._ops import _DT, compute_device
 
 ROW, SLOT, CLOUD, VOXEL = "row", "slot", "cloud", "voxel"      # how restore cuts an output: see there
+K_MIN, K_MAX = 1, 32                    # the k of knn_points and ball_query, and so the slots of the idx / d2 that group takes
+METHODS = ("walk", "grid")              # the neighbour searches of knn_points, chamfer_distance and estimate_normals
 
 
 def _err(what, msg):
@@ -18,6 +20,11 @@ def _err(what, msg):
 def _check_k(k, what, lo, hi):
     if isinstance(k, bool) or not isinstance(k, int) or not (lo <= k <= hi):
         _err(what, "k must be an int in [%d, %d], got %r" % (lo, hi, k))
+
+
+def _check_method(method, what):
+    if not isinstance(method, str) or method not in METHODS:
+        raise ValueError('%s: method must be "walk" or "grid", got %r' % (what, method))
 
 
 def _check_points(t, name, what, min_cols=3):

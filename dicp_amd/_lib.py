@@ -352,3 +352,15 @@ def check(status, what):
     if status > 0:
         raise RuntimeError("dicp_amd: %s rejected its arguments: %s" % (what, _ERRORS.get(status, status)))
     raise RuntimeError("dicp_amd: %s failed to launch: hipError_t %d" % (what, -status))
+
+
+_on = _stream = None        # _ops' (which imports this module): bound by the first call, an import per call costs as much as the call
+
+
+def call(name, device, *args):
+    """lib.<name>(*args, the current stream) with `device` current; the status is checked under the name that was called."""
+    global _on, _stream
+    if _on is None:
+        from ._ops import _on, _stream
+    with _on(device):
+        check(getattr(load(), name)(*args, _stream()), name)

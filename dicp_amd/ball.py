@@ -11,58 +11,10 @@ import math
 
 import torch
 
-from . import _clouds, _lib
-from ._clouds import ROW
-from ._ops import _DT, _p, _stream, _on
-from .knn import K_MIN, K_MAX
-
-
-class CellGrid:
-    """The cell grid of every cloud of a batch (dicp_ball_grid_build): the rows sorted by a 64-bit cell key.
-
-    pts (N,m,c) on the device, rows (N,) int32 or None, radius a (1,) device tensor of pts' dtype.  keys (N,P) int64 holding the unsigned
-    keys, perm (N,P) int32, rows4 (N,P,4) the live rows packed in sorted order, plans the per-cloud origin / cell edges / key widths /
-    live-row count, all chosen on the device.  P = dicp_ball_grid_slots(m); memory is O(m) per cloud whatever extent / radius is.
-    """
-
-    def __init__(self, pts, rows, radius):
-        self._build(pts, rows, lambda lib, dt, N, m, c: lib.dicp_ball_grid_build(
-            dt, _p(pts), c, _p(rows), N, m, _p(radius), None, _p(self.plans), _p(self.keys), _p(self.perm), _p(self.rows4), _stream()),
-            "dicp_ball_grid_build")
-
-    @classmethod
-    def by_density(cls, pts, rows):
-        """The grid without a radius (dicp_knn_grid_build), for the k-NN search: the cell edge is chosen per cloud on the device from the
-        number and the bounds of its live rows, about two rows per cell of the bounding box (csrc/dicp_gridknn.h)."""
-        self = cls.__new__(cls)
-        self._build(pts, rows, lambda lib, dt, N, m, c: lib.dicp_knn_grid_build(
-            dt, _p(pts), c, _p(rows), N, m, _p(self.plans), _p(self.keys), _p(self.perm), _p(self.rows4), _stream()), "dicp_knn_grid_build")
-        return self
-
-    def _build(self, pts, rows, call, what):
-        N, m, c = pts.shape
-        lib = _lib.load()
-        dev = pts.device
-        self.shape = (N, m, c)
-        self.slots = P = lib.dicp_ball_grid_slots(m)
-        self.plans = torch.empty((N, lib.dicp_ball_plan_bytes()), dtype=torch.uint8, device=dev)
-        self.keys = torch.empty((N, P), dtype=torch.int64, device=dev)
-        self.perm = torch.empty((N, P), dtype=torch.int32, device=dev)
-        self.rows4 = torch.empty((N, P, 4), dtype=pts.dtype, device=dev)
-        with _on(dev):
-            _lib.check(call(lib, _DT[pts.dtype], N, m, c), what)
-
-    def order(self, x, x_rows):
-        """-> (keys (N,Pn) int64, perm (N,Pn) int32): the rows of x (N,n,c) in the order of this grid's cells"""
-        N, n, c = x.shape
-        lib = _lib.load()
-        Pn = lib.dicp_ball_grid_slots(n)
-        keys = torch.empty((N, Pn), dtype=torch.int64, device=x.device)
-        perm = torch.empty((N, Pn), dtype=torch.int32, device=x.device)
-        with _on(x.device):
-            _lib.check(lib.dicp_ball_grid_build(_DT[x.dtype], _p(x), c, _p(x_rows), N, n, None, _p(self.plans), None, _p(keys), _p(perm), None,
-                                                _stream()), "dicp_ball_grid_build")
-        return keys, perm
+from . import _clouds
+from ._clouds import ROW, K_MIN, K_MAX
+from ._grid import CellGrid, _backward, _forward    # (CellGrid: also for the callers that import it from here)
+from ._ops import _DT
 
 
 class _BallQuery(torch.autograd.Function):
@@ -70,82 +22,11 @@ class _BallQuery(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, y, grid, xkeys, xperm, k, visited):
-        N, n, cx = x.shape
-        m, cy = y.shape[1], y.shape[2]
-        dt = _DT[x.dtype]
-        lib = _lib.load()
-        dev = x.device
-        ws_bytes = lib.dicp_ball_query_workspace_bytes(dt, N, n, k)
-        d2 = torch.empty((N, n, k), dtype=x.dtype, device=dev)
-        idx = torch.empty((N, n, k), dtype=torch.int64, device=dev)
-        counts = torch.empty((N, n), dtype=torch.int32, device=dev)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        with _on(dev):
-            _lib.check(lib.dicp_ball_query(dt, _p(x), cx, n, _p(xkeys), _p(xperm), _p(grid.plans), _p(grid.keys), _p(grid.perm), _p(grid.rows4),
-                                           m, N, k, _p(d2), _p(idx), _p(counts), _p(ws), ws_bytes, _p(visited), _stream()), "dicp_ball_query")
-        ctx.save_for_backward(x)
-        ctx.grid, ctx.ws, ctx.k, ctx.shape = grid, ws, k, (N, n, cx, m, cy)
-        ctx.mark_non_differentiable(idx, counts)
-        ctx.set_materialize_grads(False)
-        return d2, idx, counts
+        return _forward(ctx, "dicp_ball_query", x, y, grid, xkeys, xperm, k, True, (visited,))
 
     @staticmethod
     def backward(ctx, g_d2, _g_idx, _g_counts):
         return _backward(ctx, g_d2, 7)
-
-
-def _backward(ctx, g_d2, n_inputs):
-    """dicp_ball_query_backward from what a forward on a CellGrid saved: the gradients of x and y, None for the other inputs"""
-    nothing = (None,) * n_inputs
-    want_x, want_y = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-    if g_d2 is None or not (want_x or want_y):
-        return nothing
-    x, = ctx.saved_tensors
-    N, n, cx, m, cy = ctx.shape
-    grid = ctx.grid
-    dtype, dev = g_d2.dtype, g_d2.device
-    gx = torch.empty((N, n, cx), dtype=dtype, device=dev) if want_x else None
-    gy = torch.empty((N, m, cy), dtype=dtype, device=dev) if want_y else None
-    g_d2 = g_d2.contiguous()
-    with _on(dev):
-        _lib.check(_lib.load().dicp_ball_query_backward(_DT[dtype], _p(g_d2), _p(x), cx, n, _p(grid.rows4), _p(grid.perm), m, cy, N, ctx.k,
-                                                        _p(ctx.ws), _p(gx), _p(gy), _stream()), "dicp_ball_query_backward")
-    return (gx, gy) + nothing[2:]
-
-
-class _GridKnn(torch.autograd.Function):
-    """(x (N,n,c), y (N,m,c)) -> (d2 (N,n,k), idx (N,n,k) int64): the k nearest rows on y's density grid (dicp_knn_grid_query); the
-    backward is ball_query's."""
-
-    @staticmethod
-    def forward(ctx, x, y, grid, xkeys, xperm, k, visited, passes):
-        N, n, cx = x.shape
-        m, cy = y.shape[1], y.shape[2]
-        dt = _DT[x.dtype]
-        lib = _lib.load()
-        dev = x.device
-        ws_bytes = lib.dicp_ball_query_workspace_bytes(dt, N, n, k)
-        d2 = torch.empty((N, n, k), dtype=x.dtype, device=dev)
-        idx = torch.empty((N, n, k), dtype=torch.int64, device=dev)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        with _on(dev):
-            _lib.check(lib.dicp_knn_grid_query(dt, _p(x), cx, n, _p(xkeys), _p(xperm), _p(grid.plans), _p(grid.keys), _p(grid.perm), _p(grid.rows4),
-                                               m, N, k, _p(d2), _p(idx), _p(ws), ws_bytes, _p(visited), _p(passes), _stream()), "dicp_knn_grid_query")
-        ctx.save_for_backward(x)
-        ctx.grid, ctx.ws, ctx.k, ctx.shape = grid, ws, k, (N, n, cx, m, cy)
-        ctx.mark_non_differentiable(idx)
-        ctx.set_materialize_grads(False)
-        return d2, idx
-
-    @staticmethod
-    def backward(ctx, g_d2, _g_idx):
-        return _backward(ctx, g_d2, 8)
-
-
-def grid_knn(xb, yb, rx, grid, k, visited=None, passes=None):
-    """The k nearest rows of yb (N,m,c), whose density grid is `grid`, for every row of xb (N,n,c) -> (d2, idx) (N,n,k)"""
-    xkeys, xperm = grid.order(xb.detach(), rx)
-    return _GridKnn.apply(xb, yb, grid, xkeys, xperm, k, visited, passes)
 
 
 def _err(msg):

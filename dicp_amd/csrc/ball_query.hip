@@ -138,18 +138,18 @@ int dicp_ball_grid_build(int dtype, const void* pts, int c, const int32_t* rows,
     int rc = ball_check(dtype, N, m);
     if (rc) return rc;
     if (c < 3) return DICP_ERR_SHAPE;
-    const size_t ts = dtype == DICP_F32 ? 4 : 8;
-    if ((uintptr_t)pts % ts || (rows && (uintptr_t)rows % 4) || (radius && (uintptr_t)radius % ts) || (order_by && (uintptr_t)order_by % 8) ||
-        (plans && (uintptr_t)plans % 8) || (uintptr_t)keys % 8 || (uintptr_t)perm % 4 || (rows4 && (uintptr_t)rows4 % (4 * ts))) return DICP_ERR_ALIGN;
+    const size_t ts = elem_size(dtype);
+    if (misaligned(pts, ts) || misaligned(rows, 4) || misaligned(radius, ts) || misaligned(order_by, 8) || misaligned(plans, 8) || misaligned(keys, 8) ||
+        misaligned(perm, 4) || misaligned(rows4, 4 * ts)) return DICP_ERR_ALIGN;
     hipStream_t st = (hipStream_t)stream;
     const void* pl = order_by ? order_by : plans;
     begin_launch();
-#define DICP_BALL_BUILD(T) do { \
-        if (!order_by) ball_plan_kernel<T><<<N, BLOCK, 0, st>>>((const T*)pts, c, rows, m, (const T*)radius, plans); \
-        if ((rc = ball_grid_stages<T>((const T*)pts, c, rows, N, m, pl, order_by ? 0 : 1, keys, perm, rows4, st))) return rc; \
-    } while (0)
-    if (dtype == DICP_F32) DICP_BALL_BUILD(float); else DICP_BALL_BUILD(double);
-#undef DICP_BALL_BUILD
+    rc = with_scalar(dtype, [&](auto t) {
+        using T = decltype(t);
+        if (!order_by) ball_plan_kernel<T><<<N, BLOCK, 0, st>>>((const T*)pts, c, rows, m, (const T*)radius, plans);
+        return ball_grid_stages<T>((const T*)pts, c, rows, N, m, pl, order_by ? 0 : 1, keys, perm, rows4, st);
+    });
+    if (rc) return rc;
     return launch_status();
 }
 
@@ -161,29 +161,23 @@ size_t dicp_ball_query_workspace_bytes(int dtype, int N, int n, int k) {
 int dicp_ball_query(int dtype, const void* x, int cx, int n, const uint64_t* x_keys, const int32_t* x_perm, const void* y_plans,
                     const uint64_t* y_keys, const int32_t* y_perm, const void* y_rows4, int m, int N, int k,
                     void* d2, int64_t* idx, int32_t* counts, void* workspace, size_t workspace_bytes, unsigned long long* visited, void* stream) {
-    if (!x || !x_keys || !x_perm || !y_plans || !y_keys || !y_perm || !y_rows4 || !d2 || !idx || !counts || !workspace) return DICP_ERR_NULL;
-    int rc = ball_check(dtype, N, n);
-    if (rc || (rc = ball_check(dtype, N, m))) return rc;
-    if (cx < 3 || k < 1 || k > BALL_KMAX || workspace_bytes < dicp_ball_query_workspace_bytes(dtype, N, n, k)) return DICP_ERR_SHAPE;
-    const size_t ts = dtype == DICP_F32 ? 4 : 8;
-    if ((uintptr_t)x % ts || (uintptr_t)x_keys % 8 || (uintptr_t)x_perm % 4 || (uintptr_t)y_plans % 8 || (uintptr_t)y_keys % 8 || (uintptr_t)y_perm % 4 ||
-        (uintptr_t)y_rows4 % (4 * ts) || (uintptr_t)d2 % ts || (uintptr_t)idx % 8 || (uintptr_t)counts % 4 || (uintptr_t)workspace % 4 ||
-        (visited && (uintptr_t)visited % 8)) return DICP_ERR_ALIGN;
+    if (!counts) return DICP_ERR_NULL;
+    int rc = grid_query_check(dtype, x, cx, n, x_keys, x_perm, y_plans, y_keys, y_perm, y_rows4, m, N, k, d2, idx, workspace, workspace_bytes, visited);
+    if (rc) return rc;
+    if (misaligned(counts, 4)) return DICP_ERR_ALIGN;
     hipStream_t st = (hipStream_t)stream;
     if (visited && (rc = dicp_fill::zero(visited, (size_t)N * sizeof(unsigned long long), st))) return rc;
     const int Pn = ball_slots(n), Pm = ball_slots(m);
     const int bpc = (n + BLOCK - 1) / BLOCK;
     const unsigned g = grid_for(N, bpc);
     begin_launch();
-#define DICP_BALL(T, KK) ball_query_kernel<T, KK><<<g, BLOCK, 0, st>>>((const T*)x, cx, n, Pn, x_keys, x_perm, y_plans, y_keys, y_perm, \
-        (const V4<T>::type*)y_rows4, m, Pm, N, k, bpc, (T*)d2, idx, counts, (int32_t*)workspace, visited)
-#define DICP_BALL_T(T) do { \
-        switch (topk_kcap(k)) { \
-            case 1: DICP_BALL(T, 1); break; case 4: DICP_BALL(T, 4); break; case 8: DICP_BALL(T, 8); break; \
-            case 16: DICP_BALL(T, 16); break; default: DICP_BALL(T, 32); break; } } while (0)
-    if (dtype == DICP_F32) DICP_BALL_T(float); else DICP_BALL_T(double);
-#undef DICP_BALL_T
-#undef DICP_BALL
+    with_scalar(dtype, [&](auto t) {
+        using T = decltype(t);
+        topk_with_kcap(k, [&](auto kcap) {
+            ball_query_kernel<T, decltype(kcap)::value><<<g, BLOCK, 0, st>>>((const T*)x, cx, n, Pn, x_keys, x_perm, y_plans, y_keys, y_perm,
+                (const typename V4<T>::type*)y_rows4, m, Pm, N, k, bpc, (T*)d2, idx, counts, (int32_t*)workspace, visited);
+        });
+    });
     return launch_status();
 }
 
@@ -193,9 +187,9 @@ int dicp_ball_query_backward(int dtype, const void* g_d2, const void* x, int cx,
     int rc = ball_check(dtype, N, n);
     if (rc || (rc = ball_check(dtype, N, m))) return rc;
     if (cx < 3 || cy < 3 || k < 1 || k > BALL_KMAX) return DICP_ERR_SHAPE;
-    const size_t ts = dtype == DICP_F32 ? 4 : 8;
-    if ((uintptr_t)g_d2 % ts || (uintptr_t)x % ts || (uintptr_t)y_rows4 % (4 * ts) || (uintptr_t)y_perm % 4 || (uintptr_t)fwd_workspace % 4 ||
-        (grad_x && (uintptr_t)grad_x % ts) || (grad_y && (uintptr_t)grad_y % ts)) return DICP_ERR_ALIGN;
+    const size_t ts = elem_size(dtype);
+    if (misaligned(g_d2, ts) || misaligned(x, ts) || misaligned(y_rows4, 4 * ts) || misaligned(y_perm, 4) || misaligned(fwd_workspace, 4) ||
+        misaligned(grad_x, ts) || misaligned(grad_y, ts)) return DICP_ERR_ALIGN;
     if (!grad_x && !grad_y) return 0;
     hipStream_t st = (hipStream_t)stream;
     if (grad_y && (rc = dicp_fill::zero(grad_y, (size_t)N * m * cy * ts, st))) return rc;
@@ -203,9 +197,10 @@ int dicp_ball_query_backward(int dtype, const void* g_d2, const void* x, int cx,
     const int bpc = (n + BLOCK - 1) / BLOCK;
     const unsigned g = grid_for(N, bpc);
     begin_launch();
-#define DICP_BALL_BWD(T) ball_bwd_kernel<T><<<g, BLOCK, 0, st>>>((const T*)g_d2, (const T*)x, cx, n, (const V4<T>::type*)y_rows4, y_perm, m, Pm, cy, \
-        N, k, bpc, (const int32_t*)fwd_workspace, (T*)grad_x, (T*)grad_y)
-    if (dtype == DICP_F32) DICP_BALL_BWD(float); else DICP_BALL_BWD(double);
-#undef DICP_BALL_BWD
+    with_scalar(dtype, [&](auto t) {
+        using T = decltype(t);
+        ball_bwd_kernel<T><<<g, BLOCK, 0, st>>>((const T*)g_d2, (const T*)x, cx, n, (const typename V4<T>::type*)y_rows4, y_perm, m, Pm, cy,
+            N, k, bpc, (const int32_t*)fwd_workspace, (T*)grad_x, (T*)grad_y);
+    });
     return launch_status();
 }

@@ -105,6 +105,17 @@ inline int launch_status() {
     return e == hipSuccess ? 0 : -(int)e;
 }
 inline bool bad_dtype(int d) { return d != DICP_F32 && d != DICP_F64; }
+inline size_t elem_size(int dtype) { return dtype == DICP_F32 ? 4 : 8; }
+// (a NULL pointer, an optional argument left out, is aligned)
+inline bool misaligned(const void* p, size_t a) { return (uintptr_t)p % a != 0; }
+
+// f(T()) for the scalar type T of a checked dtype.  f is a generic lambda that starts with `using T = decltype(t);`, so the body of an
+// entry point is written once, in plain C++; what f returns is returned.
+template <typename F>
+inline auto with_scalar(int dtype, F&& f) {
+    if (dtype == DICP_F32) return f(float());
+    return f(double());
+}
 
 inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 // blocks of a grid-stride kernel over n items: one thread each, at least 1 and at most 65536 blocks

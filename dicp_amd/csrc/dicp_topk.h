@@ -16,6 +16,8 @@
 // order holds.  A NaN gap never stops the walk (the comparison is false) and a NaN or +inf d2 never enters the list (the empty tail is
 // +inf with index -1, and every row index is >= 0): a query with a non-finite coordinate walks every row and gets no neighbours.
 #pragma once
+#include <type_traits>
+
 #include "dicp_math.h"
 
 namespace dicp {
@@ -60,6 +62,19 @@ DICP_HD void topk_init(T (&d)[K], int (&id)[K], int (&sl)[K], int k) {
 
 // The list capacities the kernels are instantiated for: the smallest of 1, 4, 8, 16, 32 that holds k
 inline int topk_kcap(int k) { return k == 1 ? 1 : (k <= 4 ? 4 : (k <= 8 ? 8 : (k <= 16 ? 16 : 32))); }
+
+// f(std::integral_constant<int, K>()) for K = topk_kcap(k): f is a generic lambda that launches the kernel instantiated for K; what it
+// returns is returned.
+template <typename F>
+inline auto topk_with_kcap(int k, F&& f) {
+    switch (topk_kcap(k)) {
+        case 1: return f(std::integral_constant<int, 1>());
+        case 4: return f(std::integral_constant<int, 4>());
+        case 8: return f(std::integral_constant<int, 8>());
+        case 16: return f(std::integral_constant<int, 16>());
+        default: return f(std::integral_constant<int, 32>());
+    }
+}
 
 // (The write-out of entries K - k .. K - 1 stays an inline loop in the three kernels: as a helper taking a per-entry callable it cost
 // normals_knn_kernel<double, 16 / 32> and every ball_query_kernel 2 to 5 VGPRs, and ball_query_kernel<float, 8 / 32> a wave of occupancy.)

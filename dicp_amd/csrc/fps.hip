@@ -273,7 +273,7 @@ bool fps_streamed(int dtype, int n, int form) { return form == DICP_FPS_STREAMED
 
 struct FpsLayout { size_t rows4, slots, total; };
 inline FpsLayout fps_layout(int dtype, int N, int n) {
-    const size_t ts = dtype == DICP_F32 ? 4 : 8, ks = dtype == DICP_F32 ? sizeof(FpsKey<float>) : sizeof(FpsKey<double>);
+    const size_t ts = elem_size(dtype), ks = dtype == DICP_F32 ? sizeof(FpsKey<float>) : sizeof(FpsKey<double>);
     FpsLayout L;
     L.rows4 = 0;
     L.slots = up256((size_t)N * n * 4 * ts);
@@ -332,26 +332,25 @@ int dicp_fps_forward(int dtype, const void* pts, int c, const int32_t* rows, con
     if (form == DICP_FPS_RESIDENT && n > fps_resident_rows(dtype)) return DICP_ERR_SHAPE;
     if ((size_t)N * k >= ((size_t)1 << 40)) return DICP_ERR_SHAPE;
     const bool streamed = fps_streamed(dtype, n, form);
-    const size_t ts = dtype == DICP_F32 ? 4 : 8;
+    const size_t ts = elem_size(dtype);
     const FpsLayout L = fps_layout(dtype, N, n);
     if (streamed) {
         if (!workspace) return DICP_ERR_NULL;
         if (workspace_bytes < L.total) return DICP_ERR_SHAPE;
-        if ((uintptr_t)workspace % 256) return DICP_ERR_ALIGN;
+        if (misaligned(workspace, 256)) return DICP_ERR_ALIGN;
     }
-    if ((uintptr_t)pts % ts || (uintptr_t)out % ts || (uintptr_t)dist % ts || (uintptr_t)idx % 8 || (uintptr_t)k_eff % 4 || (uintptr_t)rows % 4 || (uintptr_t)start % 8)
+    if (misaligned(pts, ts) || misaligned(out, ts) || misaligned(dist, ts) || misaligned(idx, 8) || misaligned(k_eff, 4) || misaligned(rows, 4) || misaligned(start, 8))
         return DICP_ERR_ALIGN;
     hipStream_t st = (hipStream_t)stream;
     const size_t cells = (size_t)N * k * c;
     const unsigned gg = (unsigned)((cells + BLOCK - 1) / BLOCK);
     begin_launch();
-#define DICP_FPS_FWD(T) do { \
-        if (streamed) fps_stream<T>(pts, c, rows, start, N, n, k, idx, dist, k_eff, (char*)workspace, L, st); \
-        else fps_resident<T>(pts, c, rows, start, N, n, k, idx, dist, k_eff, st); \
-        fps_gather_kernel<T><<<gg, BLOCK, 0, st>>>((const T*)pts, idx, n, k, c, cells, (T*)out); \
-    } while (0)
-    if (dtype == DICP_F32) DICP_FPS_FWD(float); else DICP_FPS_FWD(double);
-#undef DICP_FPS_FWD
+    with_scalar(dtype, [&](auto t) {
+        using T = decltype(t);
+        if (streamed) fps_stream<T>(pts, c, rows, start, N, n, k, idx, dist, k_eff, (char*)workspace, L, st);
+        else fps_resident<T>(pts, c, rows, start, N, n, k, idx, dist, k_eff, st);
+        fps_gather_kernel<T><<<gg, BLOCK, 0, st>>>((const T*)pts, idx, n, k, c, cells, (T*)out);
+    });
     return launch_status();
 }
 
@@ -359,8 +358,8 @@ int dicp_fps_backward(int dtype, const void* grad_out, const int64_t* idx, int N
     if (!grad_out || !idx || !grad_pts) return DICP_ERR_NULL;
     int rc = fps_check(dtype, N, n, k, c);
     if (rc) return rc;
-    const size_t ts = dtype == DICP_F32 ? 4 : 8;
-    if ((uintptr_t)grad_out % ts || (uintptr_t)grad_pts % ts || (uintptr_t)idx % 8) return DICP_ERR_ALIGN;
+    const size_t ts = elem_size(dtype);
+    if (misaligned(grad_out, ts) || misaligned(grad_pts, ts) || misaligned(idx, 8)) return DICP_ERR_ALIGN;
     hipStream_t st = (hipStream_t)stream;
     if ((rc = dicp_fill::zero(grad_pts, (size_t)N * n * c * ts, st))) return rc;
     const size_t cells = (size_t)N * k * c;

@@ -19,6 +19,7 @@
 // Every kernel is a grid-stride loop of at most GROUP_MAX_BLOCKS workgroups with 64-bit element counts.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 #include "dicp_common.h"
 #include "dicp_fill.h"
@@ -442,8 +443,6 @@ __global__ __launch_bounds__(BLOCK) void pool_bwd_sum_kernel(const T* __restrict
 }
 
 // ------------------------------------------------------------------ host side
-inline size_t tsize(int dtype) { return dtype == DICP_F32 ? 4 : 8; }
-
 // a * b * c < 2^62, without overflowing on the way (every factor >= 1 and < 2^31)
 inline bool fits62(size_t a, size_t b, size_t c) {
     const size_t top = ((size_t)1 << 62) - 1;
@@ -458,17 +457,20 @@ int group_check(int dtype, int idx64, int N, int n, int m, int k, int C) {
     if (!fits62((size_t)N * n, (size_t)k, (size_t)C) || !fits62((size_t)N * m, 8, (size_t)C)) return DICP_ERR_SHAPE;
     return 0;
 }
-inline bool misaligned(const void* p, size_t a) { return p && ((uintptr_t)p % a); }
-inline bool wide(int dtype, int C) { return (size_t)C * tsize(dtype) >= GROUP_WIDE_BYTES; }
+inline bool wide(int dtype, int C) { return (size_t)C * elem_size(dtype) >= GROUP_WIDE_BYTES; }
 // rows of C elements are 16-byte segments from these bases on
-inline bool vec16(int dtype, int C, const void* a, const void* b) { return ((size_t)C * tsize(dtype)) % 16 == 0 && !(((uintptr_t)a | (uintptr_t)b) & 15); }
+inline bool vec16(int dtype, int C, const void* a, const void* b) { return ((size_t)C * elem_size(dtype)) % 16 == 0 && !(((uintptr_t)a | (uintptr_t)b) & 15); }
 
 template <typename T> struct VecOf { static constexpr int v = 16 / sizeof(T); };
 
-#define DICP_GROUP_DISPATCH(CALL) do { \
-        if (dtype == DICP_F32) { if (idx64) CALL(float, int64_t); else CALL(float, int32_t); } \
-        else                   { if (idx64) CALL(double, int64_t); else CALL(double, int32_t); } \
-    } while (0)
+// f(T(), I()) for the scalar type T of the dtype and the index type I (idx64: int64_t, else int32_t)
+template <typename F>
+inline void with_scalar_index(int dtype, int idx64, F&& f) {
+    with_scalar(dtype, [&](auto t) {
+        if (idx64) f(t, int64_t());
+        else f(t, int32_t());
+    });
+}
 
 }  // namespace
 
@@ -478,19 +480,19 @@ int dicp_group_forward(int dtype, const void* features, const void* idx, int idx
     int rc = group_check(dtype, idx64, N, n, m, k, C);
     if (rc) return rc;
     if (Cc < 0 || Cc > C) return DICP_ERR_SHAPE;
-    const size_t ts = tsize(dtype);
+    const size_t ts = elem_size(dtype);
     if (misaligned(features, ts) || misaligned(out, ts) || misaligned(centers, ts) || misaligned(idx, idx64 ? 8 : 4) || misaligned(rows, 4)) return DICP_ERR_ALIGN;
     hipStream_t st = (hipStream_t)stream;
     const size_t Q = (size_t)N * n, total = Q * k * C;
     const bool w = wide(dtype, C), v = w && vec16(dtype, C, features, out);
     begin_launch();
-#define DICP_GROUP_FWD(T, I) do { \
-        if (v)      group_fwd_wide_kernel<T, I, VecOf<T>::v><<<group_grid(Q, GW), BLOCK, 0, st>>>((const T*)features, (const I*)idx, rows, (const T*)centers, Cc, Q, n, m, k, C, (T*)out); \
-        else if (w) group_fwd_wide_kernel<T, I, 1><<<group_grid(Q, GW), BLOCK, 0, st>>>((const T*)features, (const I*)idx, rows, (const T*)centers, Cc, Q, n, m, k, C, (T*)out); \
-        else        group_fwd_narrow_kernel<T, I><<<group_grid(total, BLOCK), BLOCK, 0, st>>>((const T*)features, (const I*)idx, rows, (const T*)centers, Cc, total, n, m, k, C, (T*)out); \
-    } while (0)
-    DICP_GROUP_DISPATCH(DICP_GROUP_FWD);
-#undef DICP_GROUP_FWD
+    with_scalar_index(dtype, idx64, [&](auto t, auto i) {
+        using T = decltype(t);
+        using I = decltype(i);
+        if (v)      group_fwd_wide_kernel<T, I, VecOf<T>::v><<<group_grid(Q, GW), BLOCK, 0, st>>>((const T*)features, (const I*)idx, rows, (const T*)centers, Cc, Q, n, m, k, C, (T*)out);
+        else if (w) group_fwd_wide_kernel<T, I, 1><<<group_grid(Q, GW), BLOCK, 0, st>>>((const T*)features, (const I*)idx, rows, (const T*)centers, Cc, Q, n, m, k, C, (T*)out);
+        else        group_fwd_narrow_kernel<T, I><<<group_grid(total, BLOCK), BLOCK, 0, st>>>((const T*)features, (const I*)idx, rows, (const T*)centers, Cc, total, n, m, k, C, (T*)out);
+    });
     return launch_status();
 }
 
@@ -500,18 +502,18 @@ int dicp_group_backward(int dtype, const void* grad_out, const void* idx, int id
     int rc = group_check(dtype, idx64, N, n, m, k, C);
     if (rc) return rc;
     if (Cc < 0 || Cc > C || (grad_centers && Cc == 0)) return DICP_ERR_SHAPE;
-    const size_t ts = tsize(dtype);
+    const size_t ts = elem_size(dtype);
     if (misaligned(grad_out, ts) || misaligned(grad_features, ts) || misaligned(grad_centers, ts) || misaligned(idx, idx64 ? 8 : 4) || misaligned(rows, 4)) return DICP_ERR_ALIGN;
     hipStream_t st = (hipStream_t)stream;
     const size_t Q = (size_t)N * n, total = Q * k * C, ctotal = Q * Cc;
     if (grad_features && (rc = dicp_fill::zero(grad_features, (size_t)N * m * C * ts, st))) return rc;
     begin_launch();
-#define DICP_GROUP_BWD(T, I) do { \
-        if (grad_features) group_bwd_kernel<T, I><<<group_grid(total, BLOCK), BLOCK, 0, st>>>((const T*)grad_out, (const I*)idx, rows, total, n, m, k, C, (T*)grad_features); \
-        if (grad_centers)  group_gcenters_kernel<T, I><<<group_grid(ctotal, BLOCK), BLOCK, 0, st>>>((const T*)grad_out, (const I*)idx, rows, Cc, ctotal, n, m, k, C, (T*)grad_centers); \
-    } while (0)
-    DICP_GROUP_DISPATCH(DICP_GROUP_BWD);
-#undef DICP_GROUP_BWD
+    with_scalar_index(dtype, idx64, [&](auto t, auto i) {
+        using T = decltype(t);
+        using I = decltype(i);
+        if (grad_features) group_bwd_kernel<T, I><<<group_grid(total, BLOCK), BLOCK, 0, st>>>((const T*)grad_out, (const I*)idx, rows, total, n, m, k, C, (T*)grad_features);
+        if (grad_centers)  group_gcenters_kernel<T, I><<<group_grid(ctotal, BLOCK), BLOCK, 0, st>>>((const T*)grad_out, (const I*)idx, rows, Cc, ctotal, n, m, k, C, (T*)grad_centers);
+    });
     return launch_status();
 }
 
@@ -521,19 +523,19 @@ int dicp_interpolate_forward(int dtype, const void* features, const void* idx, i
     int rc = group_check(dtype, idx64, N, n, m, k, C);
     if (rc) return rc;
     if (!(eps > 0.0) || eps - eps != 0.0) return DICP_ERR_SHAPE;
-    const size_t ts = tsize(dtype);
+    const size_t ts = elem_size(dtype);
     if (misaligned(features, ts) || misaligned(out, ts) || misaligned(d2, ts) || misaligned(idx, idx64 ? 8 : 4) || misaligned(rows, 4)) return DICP_ERR_ALIGN;
     hipStream_t st = (hipStream_t)stream;
     const size_t Q = (size_t)N * n, total = Q * C;
     const bool w = wide(dtype, C), v = w && vec16(dtype, C, features, out);
     begin_launch();
-#define DICP_INTERP_FWD(T, I) do { \
-        if (v)      interp_fwd_wide_kernel<T, I, VecOf<T>::v><<<group_grid(Q, GW), BLOCK, 0, st>>>((const T*)features, (const I*)idx, rows, (const T*)d2, (T)eps, Q, n, m, k, C, (T*)out); \
-        else if (w) interp_fwd_wide_kernel<T, I, 1><<<group_grid(Q, GW), BLOCK, 0, st>>>((const T*)features, (const I*)idx, rows, (const T*)d2, (T)eps, Q, n, m, k, C, (T*)out); \
-        else        interp_fwd_narrow_kernel<T, I><<<group_grid(total, BLOCK), BLOCK, 0, st>>>((const T*)features, (const I*)idx, rows, (const T*)d2, (T)eps, total, n, m, k, C, (T*)out); \
-    } while (0)
-    DICP_GROUP_DISPATCH(DICP_INTERP_FWD);
-#undef DICP_INTERP_FWD
+    with_scalar_index(dtype, idx64, [&](auto t, auto i) {
+        using T = decltype(t);
+        using I = decltype(i);
+        if (v)      interp_fwd_wide_kernel<T, I, VecOf<T>::v><<<group_grid(Q, GW), BLOCK, 0, st>>>((const T*)features, (const I*)idx, rows, (const T*)d2, (T)eps, Q, n, m, k, C, (T*)out);
+        else if (w) interp_fwd_wide_kernel<T, I, 1><<<group_grid(Q, GW), BLOCK, 0, st>>>((const T*)features, (const I*)idx, rows, (const T*)d2, (T)eps, Q, n, m, k, C, (T*)out);
+        else        interp_fwd_narrow_kernel<T, I><<<group_grid(total, BLOCK), BLOCK, 0, st>>>((const T*)features, (const I*)idx, rows, (const T*)d2, (T)eps, total, n, m, k, C, (T*)out);
+    });
     return launch_status();
 }
 
@@ -543,7 +545,7 @@ int dicp_interpolate_backward(int dtype, const void* grad_out, const void* featu
     int rc = group_check(dtype, idx64, N, n, m, k, C);
     if (rc) return rc;
     if (!(eps > 0.0) || eps - eps != 0.0) return DICP_ERR_SHAPE;
-    const size_t ts = tsize(dtype);
+    const size_t ts = elem_size(dtype);
     if (misaligned(grad_out, ts) || misaligned(features, ts) || misaligned(out, ts) || misaligned(d2, ts) || misaligned(grad_features, ts) || misaligned(grad_d2, ts)
         || misaligned(idx, idx64 ? 8 : 4) || misaligned(rows, 4)) return DICP_ERR_ALIGN;
     hipStream_t st = (hipStream_t)stream;
@@ -551,14 +553,14 @@ int dicp_interpolate_backward(int dtype, const void* grad_out, const void* featu
     if (grad_features && (rc = dicp_fill::zero(grad_features, (size_t)N * m * C * ts, st))) return rc;
     const bool w = wide(dtype, C);
     begin_launch();
-#define DICP_INTERP_BWD(T, I) do { \
-        if (w) interp_bwd_wide_kernel<T, I><<<group_grid(Q, GW), BLOCK, 0, st>>>((const T*)grad_out, (const T*)features, (const T*)out, (const I*)idx, rows, (const T*)d2, (T)eps, \
-                                                                                 Q, n, m, k, C, (T*)grad_features, (T*)grad_d2); \
-        else   interp_bwd_narrow_kernel<T, I><<<group_grid(total, BLOCK), BLOCK, 0, st>>>((const T*)grad_out, (const T*)features, (const T*)out, (const I*)idx, rows, (const T*)d2, (T)eps, \
-                                                                                        total, n, m, k, C, (T*)grad_features, (T*)grad_d2); \
-    } while (0)
-    DICP_GROUP_DISPATCH(DICP_INTERP_BWD);
-#undef DICP_INTERP_BWD
+    with_scalar_index(dtype, idx64, [&](auto t, auto i) {
+        using T = decltype(t);
+        using I = decltype(i);
+        if (w) interp_bwd_wide_kernel<T, I><<<group_grid(Q, GW), BLOCK, 0, st>>>((const T*)grad_out, (const T*)features, (const T*)out, (const I*)idx, rows, (const T*)d2, (T)eps,
+                                                                                 Q, n, m, k, C, (T*)grad_features, (T*)grad_d2);
+        else   interp_bwd_narrow_kernel<T, I><<<group_grid(total, BLOCK), BLOCK, 0, st>>>((const T*)grad_out, (const T*)features, (const T*)out, (const I*)idx, rows, (const T*)d2, (T)eps,
+                                                                                        total, n, m, k, C, (T*)grad_features, (T*)grad_d2);
+    });
     return launch_status();
 }
 
@@ -570,7 +572,7 @@ int dicp_pool_forward(int dtype, const void* features, const void* idx, int idx6
     if (reduce != DICP_POOL_MAX && argmax) return DICP_ERR_ENUM;
     int rc = group_check(dtype, idx64, N, n, m, k, C);
     if (rc) return rc;
-    const size_t ts = tsize(dtype);
+    const size_t ts = elem_size(dtype);
     if (misaligned(features, ts) || misaligned(out, ts) || misaligned(argmax, 4) || misaligned(counts, 4) || misaligned(idx, idx64 ? 8 : 4) || misaligned(rows, 4)) return DICP_ERR_ALIGN;
     hipStream_t st = (hipStream_t)stream;
     const size_t Q = (size_t)N * n, total = Q * C;
@@ -578,15 +580,18 @@ int dicp_pool_forward(int dtype, const void* features, const void* idx, int idx6
     const int G = pool_lanes(v ? C / (int)(16 / ts) : C), per_block = GW * (WAVE / G), mean = reduce == DICP_POOL_MEAN;
     const size_t narrow_lds = (size_t)((BLOCK - 1) / C + 2) * (k | 1) * sizeof(int);     // at most 257 x 33 x 4 bytes
     begin_launch();
-#define DICP_POOL_FWD_R(T, I, MAX) do { \
-        if (v)      pool_fwd_wide_kernel<T, I, VecOf<T>::v, MAX><<<group_grid(Q, per_block), BLOCK, 0, st>>>((const T*)features, (const I*)idx, rows, Q, n, m, k, C, G, mean, (T*)out, argmax, counts); \
-        else if (w) pool_fwd_wide_kernel<T, I, 1, MAX><<<group_grid(Q, per_block), BLOCK, 0, st>>>((const T*)features, (const I*)idx, rows, Q, n, m, k, C, G, mean, (T*)out, argmax, counts); \
-        else        pool_fwd_narrow_kernel<T, I, MAX><<<group_grid(total, BLOCK), BLOCK, narrow_lds, st>>>((const T*)features, (const I*)idx, rows, total, n, m, k, C, mean, (T*)out, argmax, counts); \
-    } while (0)
-#define DICP_POOL_FWD(T, I) do { if (reduce == DICP_POOL_MAX) DICP_POOL_FWD_R(T, I, true); else DICP_POOL_FWD_R(T, I, false); } while (0)
-    DICP_GROUP_DISPATCH(DICP_POOL_FWD);
-#undef DICP_POOL_FWD
-#undef DICP_POOL_FWD_R
+    with_scalar_index(dtype, idx64, [&](auto t, auto i) {
+        using T = decltype(t);
+        using I = decltype(i);
+        auto launch = [&](auto is_max) {
+            constexpr bool MAX = decltype(is_max)::value;
+            if (v)      pool_fwd_wide_kernel<T, I, VecOf<T>::v, MAX><<<group_grid(Q, per_block), BLOCK, 0, st>>>((const T*)features, (const I*)idx, rows, Q, n, m, k, C, G, mean, (T*)out, argmax, counts);
+            else if (w) pool_fwd_wide_kernel<T, I, 1, MAX><<<group_grid(Q, per_block), BLOCK, 0, st>>>((const T*)features, (const I*)idx, rows, Q, n, m, k, C, G, mean, (T*)out, argmax, counts);
+            else        pool_fwd_narrow_kernel<T, I, MAX><<<group_grid(total, BLOCK), BLOCK, narrow_lds, st>>>((const T*)features, (const I*)idx, rows, total, n, m, k, C, mean, (T*)out, argmax, counts);
+        };
+        if (reduce == DICP_POOL_MAX) launch(std::true_type());
+        else launch(std::false_type());
+    });
     return launch_status();
 }
 
@@ -598,7 +603,7 @@ int dicp_pool_backward(int dtype, const void* grad_out, const void* idx, int idx
     if (reduce != DICP_POOL_MAX && argmax) return DICP_ERR_ENUM;
     int rc = group_check(dtype, idx64, N, n, m, k, C);
     if (rc) return rc;
-    const size_t ts = tsize(dtype);
+    const size_t ts = elem_size(dtype);
     if (misaligned(grad_out, ts) || misaligned(grad_features, ts) || misaligned(argmax, 4) || misaligned(counts, 4) || misaligned(idx, idx64 ? 8 : 4) || misaligned(rows, 4)) return DICP_ERR_ALIGN;
     hipStream_t st = (hipStream_t)stream;
     const size_t Q = (size_t)N * n, qc = Q * C, total = qc * k;
@@ -609,9 +614,11 @@ int dicp_pool_backward(int dtype, const void* grad_out, const void* idx, int idx
         if (dtype == DICP_F32) pool_bwd_max_kernel<float><<<group_grid(qc, BLOCK), BLOCK, 0, st>>>((const float*)grad_out, argmax, rows, qc, n, m, C, (float*)grad_features);
         else                   pool_bwd_max_kernel<double><<<group_grid(qc, BLOCK), BLOCK, 0, st>>>((const double*)grad_out, argmax, rows, qc, n, m, C, (double*)grad_features);
     } else {
-#define DICP_POOL_BWD(T, I) pool_bwd_sum_kernel<T, I><<<group_grid(total, BLOCK), BLOCK, 0, st>>>((const T*)grad_out, (const I*)idx, rows, cnt, total, n, m, k, C, (T*)grad_features)
-        DICP_GROUP_DISPATCH(DICP_POOL_BWD);
-#undef DICP_POOL_BWD
+        with_scalar_index(dtype, idx64, [&](auto t, auto i) {
+            using T = decltype(t);
+            using I = decltype(i);
+            pool_bwd_sum_kernel<T, I><<<group_grid(total, BLOCK), BLOCK, 0, st>>>((const T*)grad_out, (const I*)idx, rows, cnt, total, n, m, k, C, (T*)grad_features);
+        });
     }
     return launch_status();
 }

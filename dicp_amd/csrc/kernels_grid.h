@@ -154,6 +154,20 @@ int ball_check(int dtype, int N, int m) {
     return 0;
 }
 
+// The arguments dicp_ball_query and dicp_knn_grid_query have in common, checked in the order that decides the status of a bad call
+int grid_query_check(int dtype, const void* x, int cx, int n, const uint64_t* x_keys, const int32_t* x_perm, const void* y_plans,
+                     const uint64_t* y_keys, const int32_t* y_perm, const void* y_rows4, int m, int N, int k, const void* d2, const int64_t* idx,
+                     const void* workspace, size_t workspace_bytes, const unsigned long long* visited) {
+    if (!x || !x_keys || !x_perm || !y_plans || !y_keys || !y_perm || !y_rows4 || !d2 || !idx || !workspace) return DICP_ERR_NULL;
+    int rc = ball_check(dtype, N, n);
+    if (rc || (rc = ball_check(dtype, N, m))) return rc;
+    if (cx < 3 || k < 1 || k > BALL_KMAX || workspace_bytes < up256((size_t)N * n * k * 4)) return DICP_ERR_SHAPE;
+    const size_t ts = elem_size(dtype);
+    if (misaligned(x, ts) || misaligned(x_keys, 8) || misaligned(x_perm, 4) || misaligned(y_plans, 8) || misaligned(y_keys, 8) || misaligned(y_perm, 4) ||
+        misaligned(y_rows4, 4 * ts) || misaligned(d2, ts) || misaligned(idx, 8) || misaligned(workspace, 4) || misaligned(visited, 8)) return DICP_ERR_ALIGN;
+    return 0;
+}
+
 int ball_sort(uint64_t* key, int32_t* idx, int N, int P, hipStream_t st) {
     const int chunk = P < BALL_CHUNK ? P : BALL_CHUNK;
     const size_t chunks = (size_t)N * (P / chunk), pairs = (size_t)N * (P / 2);

@@ -75,9 +75,8 @@ int dicp_knn_grid_build(int dtype, const void* pts, int c, const int32_t* rows, 
     int rc = ball_check(dtype, N, m);
     if (rc) return rc;
     if (c < 3) return DICP_ERR_SHAPE;
-    const size_t ts = dtype == DICP_F32 ? 4 : 8;
-    if ((uintptr_t)pts % ts || (rows && (uintptr_t)rows % 4) || (uintptr_t)plans % 8 || (uintptr_t)keys % 8 || (uintptr_t)perm % 4 ||
-        (uintptr_t)rows4 % (4 * ts)) return DICP_ERR_ALIGN;
+    const size_t ts = elem_size(dtype);
+    if (misaligned(pts, ts) || misaligned(rows, 4) || misaligned(plans, 8) || misaligned(keys, 8) || misaligned(perm, 4) || misaligned(rows4, 4 * ts)) return DICP_ERR_ALIGN;
     hipStream_t st = (hipStream_t)stream;
     begin_launch();
     rc = dtype == DICP_F32 ? gknn_grid_build<float>((const float*)pts, c, rows, N, m, plans, keys, perm, rows4, st)
@@ -90,14 +89,9 @@ int dicp_knn_grid_query(int dtype, const void* x, int cx, int n, const uint64_t*
                         const uint64_t* y_keys, const int32_t* y_perm, const void* y_rows4, int m, int N, int k,
                         void* d2, int64_t* idx, void* workspace, size_t workspace_bytes, unsigned long long* visited, unsigned long long* passes,
                         void* stream) {
-    if (!x || !x_keys || !x_perm || !y_plans || !y_keys || !y_perm || !y_rows4 || !d2 || !idx || !workspace) return DICP_ERR_NULL;
-    int rc = ball_check(dtype, N, n);
-    if (rc || (rc = ball_check(dtype, N, m))) return rc;
-    if (cx < 3 || k < 1 || k > BALL_KMAX || workspace_bytes < up256((size_t)N * n * k * 4)) return DICP_ERR_SHAPE;
-    const size_t ts = dtype == DICP_F32 ? 4 : 8;
-    if ((uintptr_t)x % ts || (uintptr_t)x_keys % 8 || (uintptr_t)x_perm % 4 || (uintptr_t)y_plans % 8 || (uintptr_t)y_keys % 8 || (uintptr_t)y_perm % 4 ||
-        (uintptr_t)y_rows4 % (4 * ts) || (uintptr_t)d2 % ts || (uintptr_t)idx % 8 || (uintptr_t)workspace % 4 ||
-        (visited && (uintptr_t)visited % 8) || (passes && (uintptr_t)passes % 8)) return DICP_ERR_ALIGN;
+    int rc = grid_query_check(dtype, x, cx, n, x_keys, x_perm, y_plans, y_keys, y_perm, y_rows4, m, N, k, d2, idx, workspace, workspace_bytes, visited);
+    if (rc) return rc;
+    if (misaligned(passes, 8)) return DICP_ERR_ALIGN;
     hipStream_t st = (hipStream_t)stream;
     if (visited && (rc = dicp_fill::zero(visited, (size_t)N * sizeof(unsigned long long), st))) return rc;
     if (passes && (rc = dicp_fill::zero(passes, (size_t)N * sizeof(unsigned long long), st))) return rc;
@@ -105,14 +99,12 @@ int dicp_knn_grid_query(int dtype, const void* x, int cx, int n, const uint64_t*
     const int bpc = (n + BLOCK - 1) / BLOCK;
     const unsigned g = grid_for(N, bpc);
     begin_launch();
-#define DICP_GKNN(T, KK) gknn_query_kernel<T, KK><<<g, BLOCK, 0, st>>>((const T*)x, cx, n, Pn, x_keys, x_perm, y_plans, y_keys, y_perm, \
-        (const V4<T>::type*)y_rows4, Pm, N, k, bpc, (T*)d2, idx, (int32_t*)workspace, visited, passes)
-#define DICP_GKNN_T(T) do { \
-        switch (topk_kcap(k)) { \
-            case 1: DICP_GKNN(T, 1); break; case 4: DICP_GKNN(T, 4); break; case 8: DICP_GKNN(T, 8); break; \
-            case 16: DICP_GKNN(T, 16); break; default: DICP_GKNN(T, 32); break; } } while (0)
-    if (dtype == DICP_F32) DICP_GKNN_T(float); else DICP_GKNN_T(double);
-#undef DICP_GKNN_T
-#undef DICP_GKNN
+    with_scalar(dtype, [&](auto t) {
+        using T = decltype(t);
+        topk_with_kcap(k, [&](auto kcap) {
+            gknn_query_kernel<T, decltype(kcap)::value><<<g, BLOCK, 0, st>>>((const T*)x, cx, n, Pn, x_keys, x_perm, y_plans, y_keys, y_perm,
+                (const typename V4<T>::type*)y_rows4, Pm, N, k, bpc, (T*)d2, idx, (int32_t*)workspace, visited, passes);
+        });
+    });
     return launch_status();
 }

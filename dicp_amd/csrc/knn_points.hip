@@ -181,7 +181,7 @@ int knn_check(int dtype, int N, int n, int m, int k) {
 
 size_t dicp_knn_points_workspace_bytes(int dtype, int N, int n, int m, int k, int backward) {
     if (knn_check(dtype, N, n, m, k)) return 0;
-    const size_t ts = dtype == DICP_F32 ? 4 : 8;
+    const size_t ts = elem_size(dtype);
     if (backward) return up256((size_t)N * dicp_padded_targets(m) * 3 * ts);
     return up256((size_t)N * dicp_padded_targets(n) * k * 4);
 }
@@ -193,10 +193,10 @@ int dicp_knn_points(int dtype, const void* x_tgs4, const int32_t* x_perm, const 
     int rc = knn_check(dtype, N, n, m, k);
     if (rc) return rc;
     if (workspace_bytes < dicp_knn_points_workspace_bytes(dtype, N, n, m, k, 0)) return DICP_ERR_SHAPE;
-    const size_t ts = dtype == DICP_F32 ? 4 : 8;
-    if ((uintptr_t)x_tgs4 % (4 * ts) || (uintptr_t)y_tgs4 % (4 * ts) || (uintptr_t)y_keys % ts || (uintptr_t)x_perm % 4 || (uintptr_t)y_perm % 4 ||
-        (uintptr_t)d2 % ts || (uintptr_t)idx % 8 || (uintptr_t)workspace % 4 || (x_rows && (uintptr_t)x_rows % 4) || (y_rows && (uintptr_t)y_rows % 4) ||
-        (walked && (uintptr_t)walked % 8)) return DICP_ERR_ALIGN;
+    const size_t ts = elem_size(dtype);
+    if (misaligned(x_tgs4, 4 * ts) || misaligned(y_tgs4, 4 * ts) || misaligned(y_keys, ts) || misaligned(x_perm, 4) || misaligned(y_perm, 4) ||
+        misaligned(d2, ts) || misaligned(idx, 8) || misaligned(workspace, 4) || misaligned(x_rows, 4) || misaligned(y_rows, 4) ||
+        misaligned(walked, 8)) return DICP_ERR_ALIGN;
     hipStream_t st = (hipStream_t)stream;
     if (walked && (rc = dicp_fill::zero(walked, (size_t)N * sizeof(unsigned long long), st))) return rc;
     const int n_pad = dicp_padded_targets(n), m_pad = dicp_padded_targets(m);
@@ -204,15 +204,13 @@ int dicp_knn_points(int dtype, const void* x_tgs4, const int32_t* x_perm, const 
     const unsigned g = grid_for(N, bpc);
     int32_t* slots = (int32_t*)workspace;
     begin_launch();
-#define DICP_KNN(T, KK) knn_points_kernel<T, KK><<<g, BLOCK, 0, st>>>((const V4<T>::type*)x_tgs4, x_perm, x_rows, n, n_pad, (const T*)y_keys, \
-        (const V4<T>::type*)y_tgs4, y_perm, y_rows, m, m_pad, N, k, bpc, (T*)d2, idx, slots, walked)
-#define DICP_KNN_T(T) do { \
-        switch (topk_kcap(k)) { \
-            case 1: DICP_KNN(T, 1); break; case 4: DICP_KNN(T, 4); break; case 8: DICP_KNN(T, 8); break; \
-            case 16: DICP_KNN(T, 16); break; default: DICP_KNN(T, 32); break; } } while (0)
-    if (dtype == DICP_F32) DICP_KNN_T(float); else DICP_KNN_T(double);
-#undef DICP_KNN_T
-#undef DICP_KNN
+    with_scalar(dtype, [&](auto t) {
+        using T = decltype(t);
+        topk_with_kcap(k, [&](auto kcap) {
+            knn_points_kernel<T, decltype(kcap)::value><<<g, BLOCK, 0, st>>>((const typename V4<T>::type*)x_tgs4, x_perm, x_rows, n, n_pad, (const T*)y_keys,
+                (const typename V4<T>::type*)y_tgs4, y_perm, y_rows, m, m_pad, N, k, bpc, (T*)d2, idx, slots, walked);
+        });
+    });
     return launch_status();
 }
 
@@ -224,10 +222,9 @@ int dicp_knn_points_backward(int dtype, const void* g_d2, const void* x_tgs4, co
     int rc = knn_check(dtype, N, n, m, k);
     if (rc) return rc;
     if (cx < 3 || cy < 3 || (grad_y && workspace_bytes < dicp_knn_points_workspace_bytes(dtype, N, n, m, k, 1))) return DICP_ERR_SHAPE;
-    const size_t ts = dtype == DICP_F32 ? 4 : 8;
-    if ((uintptr_t)g_d2 % ts || (uintptr_t)x_tgs4 % (4 * ts) || (uintptr_t)y_tgs4 % (4 * ts) || (uintptr_t)x_perm % 4 || (uintptr_t)y_perm % 4 ||
-        (uintptr_t)fwd_workspace % 4 || (x_rows && (uintptr_t)x_rows % 4) || (grad_x && (uintptr_t)grad_x % ts) || (grad_y && (uintptr_t)grad_y % ts) ||
-        (workspace && (uintptr_t)workspace % 16)) return DICP_ERR_ALIGN;
+    const size_t ts = elem_size(dtype);
+    if (misaligned(g_d2, ts) || misaligned(x_tgs4, 4 * ts) || misaligned(y_tgs4, 4 * ts) || misaligned(x_perm, 4) || misaligned(y_perm, 4) ||
+        misaligned(fwd_workspace, 4) || misaligned(x_rows, 4) || misaligned(grad_x, ts) || misaligned(grad_y, ts) || misaligned(workspace, 16)) return DICP_ERR_ALIGN;
     if (!grad_x && !grad_y) return 0;
     hipStream_t st = (hipStream_t)stream;
     const int n_pad = dicp_padded_targets(n), m_pad = dicp_padded_targets(m);
@@ -238,10 +235,11 @@ int dicp_knn_points_backward(int dtype, const void* g_d2, const void* x_tgs4, co
     const int bpc = (n + BLOCK - 1) / BLOCK;
     const unsigned g = grid_for(N, bpc);
     begin_launch();
-#define DICP_KNN_BWD(T) knn_points_bwd_kernel<T><<<g, BLOCK, 0, st>>>((const T*)g_d2, (const V4<T>::type*)x_tgs4, x_perm, x_rows, n, n_pad, \
-        (const V4<T>::type*)y_tgs4, m_pad, N, k, bpc, (const int32_t*)fwd_workspace, (T*)grad_x, cx, (T*)(grad_y ? workspace : nullptr))
-    if (dtype == DICP_F32) DICP_KNN_BWD(float); else DICP_KNN_BWD(double);
-#undef DICP_KNN_BWD
+    with_scalar(dtype, [&](auto t) {
+        using T = decltype(t);
+        knn_points_bwd_kernel<T><<<g, BLOCK, 0, st>>>((const T*)g_d2, (const typename V4<T>::type*)x_tgs4, x_perm, x_rows, n, n_pad,
+            (const typename V4<T>::type*)y_tgs4, m_pad, N, k, bpc, (const int32_t*)fwd_workspace, (T*)grad_x, cx, (T*)(grad_y ? workspace : nullptr));
+    });
     if ((rc = launch_status()) || !grad_y) return rc;
     return dicp_permute_add_rows(dtype, workspace, y_perm, N, m_pad, m_pad, m_pad, 3, 3, grad_y, m, cy, stream);
 }

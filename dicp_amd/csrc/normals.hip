@@ -39,6 +39,7 @@
 namespace {
 
 constexpr int NRM_KMAX = 32;
+constexpr int NRM_KCAP_MIN = 8;                         // no list below 8 (k >= 3): the walk kernels are not instantiated for capacities 1 and 4
 template <typename T> struct WalkHalo;                  // LDS rows staged on either side of a block's slots: 36 KiB float4 / 40 KiB double4
 template <> struct WalkHalo<float>  { static constexpr int v = 1024; };
 template <> struct WalkHalo<double> { static constexpr int v = 512; };
@@ -56,7 +57,7 @@ struct NrmLayout {
 };
 inline NrmLayout nrm_layout(int dtype, int N, int m, int k) {
     NrmLayout L;
-    const size_t ts = dtype == DICP_F32 ? 4 : 8, m_pad = (size_t)dicp_padded_targets(m);
+    const size_t ts = elem_size(dtype), m_pad = (size_t)dicp_padded_targets(m);
     size_t off = 0;
     L.xyz = off;     off = up256(off + (size_t)N * m * 3 * ts);
     L.keys = off;    off = up256(off + (size_t)N * m_pad * ts);
@@ -75,7 +76,7 @@ struct NrmGridLayout {
 };
 inline NrmGridLayout nrm_grid_layout(int dtype, int N, int m, int k) {
     NrmGridLayout L;
-    const size_t ts = dtype == DICP_F32 ? 4 : 8, P = (size_t)ball_slots(m);
+    const size_t ts = elem_size(dtype), P = (size_t)ball_slots(m);
     size_t off = 0;
     L.plans = off;   off = up256(off + (size_t)N * BALL_PLAN_BYTES);
     L.keys = off;    off = up256(off + (size_t)N * P * 8);
@@ -335,7 +336,7 @@ int nrm_grid_check(int dtype, int N, int m, int k, int c, int vp_per_cloud) {
 
 size_t dicp_normals_workspace_bytes(int dtype, int N, int m, int k, int c, int backward) {
     if (nrm_check(dtype, N, m, k, 0) || c < 3) return 0;
-    const size_t ts = dtype == DICP_F32 ? 4 : 8;
+    const size_t ts = elem_size(dtype);
     if (backward) return up256((size_t)N * dicp_padded_targets(m) * 3 * ts);
     return nrm_layout(dtype, N, m, k).total;
 }
@@ -349,9 +350,9 @@ int dicp_normals_forward(int dtype, const void* pts, int c, const int32_t* rows,
     if (c < 3) return DICP_ERR_SHAPE;
     const NrmLayout L = nrm_layout(dtype, N, m, k);
     if (workspace_bytes < L.total) return DICP_ERR_SHAPE;
-    const size_t ts = dtype == DICP_F32 ? 4 : 8;
-    if ((uintptr_t)workspace % 256 || (uintptr_t)pts % ts || (uintptr_t)normals % ts || (curvature && (uintptr_t)curvature % ts) ||
-        (neighbors && (uintptr_t)neighbors % 8) || (viewpoint && (uintptr_t)viewpoint % ts)) return DICP_ERR_ALIGN;
+    const size_t ts = elem_size(dtype);
+    if (misaligned(workspace, 256) || misaligned(pts, ts) || misaligned(normals, ts) || misaligned(curvature, ts) || misaligned(neighbors, 8) ||
+        misaligned(viewpoint, ts)) return DICP_ERR_ALIGN;
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
     const int m_pad = dicp_padded_targets(m);
@@ -373,15 +374,15 @@ int dicp_normals_forward(int dtype, const void* pts, int c, const int32_t* rows,
     const unsigned g = grid_for(N, bpc);
     const int vs = vp_per_cloud ? 3 : 0;
     begin_launch();
-#define DICP_NRM_KNN(T, KK) normals_knn_kernel<T, KK><<<g, BLOCK, 0, st>>>((const V4<T>::type*)(ws + L.tgs4), tperm, rows, N, m, m_pad, k, bpc, nbr_s, neighbors, walked)
-#define DICP_NRM(T) do { \
-        const int kc = topk_kcap(k < 8 ? 8 : k);   /* (no list below 8) */ \
-        if (kc == 8) DICP_NRM_KNN(T, 8); else if (kc == 16) DICP_NRM_KNN(T, 16); else DICP_NRM_KNN(T, 32); \
-        normals_point_kernel<T, false><<<g, BLOCK, 0, st>>>((const V4<T>::type*)(ws + L.tgs4), tperm, rows, nullptr, N, m, m_pad, k, bpc, nbr_s, (const T*)viewpoint, vs, \
-                                                      (T*)normals, (T*)curvature); } while (0)
-    if (dtype == DICP_F32) DICP_NRM(float); else DICP_NRM(double);
-#undef DICP_NRM
-#undef DICP_NRM_KNN
+    with_scalar(dtype, [&](auto t) {
+        using T = decltype(t);
+        const auto* tgs4 = (const typename V4<T>::type*)(ws + L.tgs4);
+        topk_with_kcap(k < NRM_KCAP_MIN ? NRM_KCAP_MIN : k, [&](auto kcap) {
+            constexpr int K = decltype(kcap)::value;
+            if constexpr (K >= NRM_KCAP_MIN) normals_knn_kernel<T, K><<<g, BLOCK, 0, st>>>(tgs4, tperm, rows, N, m, m_pad, k, bpc, nbr_s, neighbors, walked);
+        });
+        normals_point_kernel<T, false><<<g, BLOCK, 0, st>>>(tgs4, tperm, rows, nullptr, N, m, m_pad, k, bpc, nbr_s, (const T*)viewpoint, vs, (T*)normals, (T*)curvature);
+    });
     return launch_status();
 }
 
@@ -391,9 +392,9 @@ int dicp_normals_backward(int dtype, const void* g_normals, const void* g_curvat
     int rc = nrm_check(dtype, N, m, k, vp_per_cloud);
     if (rc) return rc;
     if (c < 3 || workspace_bytes < dicp_normals_workspace_bytes(dtype, N, m, k, c, 1)) return DICP_ERR_SHAPE;
-    const size_t ts = dtype == DICP_F32 ? 4 : 8;
-    if ((uintptr_t)fwd_workspace % 256 || (uintptr_t)workspace % 16 || (uintptr_t)grad_pts % ts || (g_normals && (uintptr_t)g_normals % ts) ||
-        (g_curvature && (uintptr_t)g_curvature % ts) || (viewpoint && (uintptr_t)viewpoint % ts)) return DICP_ERR_ALIGN;
+    const size_t ts = elem_size(dtype);
+    if (misaligned(fwd_workspace, 256) || misaligned(workspace, 16) || misaligned(grad_pts, ts) || misaligned(g_normals, ts) || misaligned(g_curvature, ts) ||
+        misaligned(viewpoint, ts)) return DICP_ERR_ALIGN;
     hipStream_t st = (hipStream_t)stream;
     const NrmLayout L = nrm_layout(dtype, N, m, k);
     const char* ws = (const char*)fwd_workspace;
@@ -407,17 +408,18 @@ int dicp_normals_backward(int dtype, const void* g_normals, const void* g_curvat
     const unsigned g = grid_for(N, bpc);
     const int vs = vp_per_cloud ? 3 : 0;
     begin_launch();
-#define DICP_NRM_BWD(T) normals_bwd_kernel<T, false><<<g, BLOCK, 0, st>>>((const V4<T>::type*)(ws + L.tgs4), tperm, rows, nullptr, N, m, m_pad, k, bpc, \
-        (const int32_t*)(ws + L.nbr_s), (const T*)viewpoint, vs, (const T*)g_normals, (const T*)g_curvature, (T*)workspace)
-    if (dtype == DICP_F32) DICP_NRM_BWD(float); else DICP_NRM_BWD(double);
-#undef DICP_NRM_BWD
+    with_scalar(dtype, [&](auto t) {
+        using T = decltype(t);
+        normals_bwd_kernel<T, false><<<g, BLOCK, 0, st>>>((const typename V4<T>::type*)(ws + L.tgs4), tperm, rows, nullptr, N, m, m_pad, k, bpc,
+            (const int32_t*)(ws + L.nbr_s), (const T*)viewpoint, vs, (const T*)g_normals, (const T*)g_curvature, (T*)workspace);
+    });
     if ((rc = launch_status())) return rc;
     return dicp_permute_add_rows(dtype, workspace, tperm, N, m_pad, m_pad, m_pad, 3, 3, grad_pts, m, c, stream);
 }
 
 size_t dicp_normals_grid_workspace_bytes(int dtype, int N, int m, int k, int c, int backward) {
     if (nrm_grid_check(dtype, N, m, k, c, 0)) return 0;
-    const size_t ts = dtype == DICP_F32 ? 4 : 8;
+    const size_t ts = elem_size(dtype);
     if (backward) return up256((size_t)N * ball_slots(m) * 3 * ts);
     return nrm_grid_layout(dtype, N, m, k).total;
 }
@@ -430,10 +432,9 @@ int dicp_normals_grid_forward(int dtype, const void* pts, int c, const int32_t* 
     if (rc) return rc;
     const NrmGridLayout L = nrm_grid_layout(dtype, N, m, k);
     if (workspace_bytes < L.total) return DICP_ERR_SHAPE;
-    const size_t ts = dtype == DICP_F32 ? 4 : 8;
-    if ((uintptr_t)workspace % 256 || (uintptr_t)pts % ts || (rows && (uintptr_t)rows % 4) || (uintptr_t)normals % ts ||
-        (curvature && (uintptr_t)curvature % ts) || (neighbors && (uintptr_t)neighbors % 8) || (viewpoint && (uintptr_t)viewpoint % ts) ||
-        (visited && (uintptr_t)visited % 8) || (passes && (uintptr_t)passes % 8)) return DICP_ERR_ALIGN;
+    const size_t ts = elem_size(dtype);
+    if (misaligned(workspace, 256) || misaligned(pts, ts) || misaligned(rows, 4) || misaligned(normals, ts) || misaligned(curvature, ts) ||
+        misaligned(neighbors, 8) || misaligned(viewpoint, ts) || misaligned(visited, 8) || misaligned(passes, 8)) return DICP_ERR_ALIGN;
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
     void* plans = ws + L.plans;
@@ -447,17 +448,18 @@ int dicp_normals_grid_forward(int dtype, const void* pts, int c, const int32_t* 
     const unsigned g = grid_for(N, bpc);
     const int vs = vp_per_cloud ? 3 : 0;
     begin_launch();
-#define DICP_NRM_GKNN(T, KK) normals_grid_knn_kernel<T, KK><<<g, BLOCK, 0, st>>>(plans, keys, perm, (const V4<T>::type*)(ws + L.rows4), N, m, P, k, bpc, \
-        nbr_s, neighbors, visited, passes)
-#define DICP_NRM_GRID(T) do { \
-        if ((rc = gknn_grid_build<T>((const T*)pts, c, rows, N, m, plans, keys, perm, ws + L.rows4, st))) return rc; \
-        const int kc = topk_kcap(k < 8 ? 8 : k);   /* (no list below 8) */ \
-        if (kc == 8) DICP_NRM_GKNN(T, 8); else if (kc == 16) DICP_NRM_GKNN(T, 16); else DICP_NRM_GKNN(T, 32); \
-        normals_point_kernel<T, true><<<g, BLOCK, 0, st>>>((const V4<T>::type*)(ws + L.rows4), perm, nullptr, plans, N, m, P, k, bpc, nbr_s, \
-                                                           (const T*)viewpoint, vs, (T*)normals, (T*)curvature); } while (0)
-    if (dtype == DICP_F32) DICP_NRM_GRID(float); else DICP_NRM_GRID(double);
-#undef DICP_NRM_GRID
-#undef DICP_NRM_GKNN
+    rc = with_scalar(dtype, [&](auto t) {
+        using T = decltype(t);
+        const auto* rows4 = (const typename V4<T>::type*)(ws + L.rows4);
+        if (const int e = gknn_grid_build<T>((const T*)pts, c, rows, N, m, plans, keys, perm, ws + L.rows4, st)) return e;
+        topk_with_kcap(k < NRM_KCAP_MIN ? NRM_KCAP_MIN : k, [&](auto kcap) {
+            constexpr int K = decltype(kcap)::value;
+            if constexpr (K >= NRM_KCAP_MIN) normals_grid_knn_kernel<T, K><<<g, BLOCK, 0, st>>>(plans, keys, perm, rows4, N, m, P, k, bpc, nbr_s, neighbors, visited, passes);
+        });
+        normals_point_kernel<T, true><<<g, BLOCK, 0, st>>>(rows4, perm, nullptr, plans, N, m, P, k, bpc, nbr_s, (const T*)viewpoint, vs, (T*)normals, (T*)curvature);
+        return 0;
+    });
+    if (rc) return rc;
     return launch_status();
 }
 
@@ -467,9 +469,9 @@ int dicp_normals_grid_backward(int dtype, const void* g_normals, const void* g_c
     int rc = nrm_grid_check(dtype, N, m, k, c, vp_per_cloud);
     if (rc) return rc;
     if (workspace_bytes < dicp_normals_grid_workspace_bytes(dtype, N, m, k, c, 1)) return DICP_ERR_SHAPE;
-    const size_t ts = dtype == DICP_F32 ? 4 : 8;
-    if ((uintptr_t)fwd_workspace % 256 || (uintptr_t)workspace % 16 || (uintptr_t)grad_pts % ts || (g_normals && (uintptr_t)g_normals % ts) ||
-        (g_curvature && (uintptr_t)g_curvature % ts) || (viewpoint && (uintptr_t)viewpoint % ts)) return DICP_ERR_ALIGN;
+    const size_t ts = elem_size(dtype);
+    if (misaligned(fwd_workspace, 256) || misaligned(workspace, 16) || misaligned(grad_pts, ts) || misaligned(g_normals, ts) || misaligned(g_curvature, ts) ||
+        misaligned(viewpoint, ts)) return DICP_ERR_ALIGN;
     hipStream_t st = (hipStream_t)stream;
     const NrmGridLayout L = nrm_grid_layout(dtype, N, m, k);
     const char* ws = (const char*)fwd_workspace;
@@ -482,10 +484,11 @@ int dicp_normals_grid_backward(int dtype, const void* g_normals, const void* g_c
     const unsigned g = grid_for(N, bpc);
     const int vs = vp_per_cloud ? 3 : 0;
     begin_launch();
-#define DICP_NRM_BWD(T) normals_bwd_kernel<T, true><<<g, BLOCK, 0, st>>>((const V4<T>::type*)(ws + L.rows4), perm, nullptr, ws + L.plans, N, m, P, k, bpc, \
-        (const int32_t*)(ws + L.nbr_s), (const T*)viewpoint, vs, (const T*)g_normals, (const T*)g_curvature, (T*)workspace)
-    if (dtype == DICP_F32) DICP_NRM_BWD(float); else DICP_NRM_BWD(double);
-#undef DICP_NRM_BWD
+    with_scalar(dtype, [&](auto t) {
+        using T = decltype(t);
+        normals_bwd_kernel<T, true><<<g, BLOCK, 0, st>>>((const typename V4<T>::type*)(ws + L.rows4), perm, nullptr, ws + L.plans, N, m, P, k, bpc,
+            (const int32_t*)(ws + L.nbr_s), (const T*)viewpoint, vs, (const T*)g_normals, (const T*)g_curvature, (T*)workspace);
+    });
     if ((rc = launch_status())) return rc;
     return dicp_permute_add_rows(dtype, workspace, perm, N, m, P, P, 3, 3, grad_pts, m, c, stream);   // (slots 0 .. m - 1 hold the cloud's m rows)
 }

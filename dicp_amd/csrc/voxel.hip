@@ -618,9 +618,8 @@ int dicp_voxel_count(int dtype, const void* pts, int c, const int32_t* rows, int
     if (!(sx > 0 && sy > 0 && sz > 0) || !(sx < HUGE_VAL && sy < HUGE_VAL && sz < HUGE_VAL)) return DICP_ERR_SHAPE;
     const VoxLayout L = vox_layout(N, m);
     if (workspace_bytes < L.total) return DICP_ERR_SHAPE;
-    const size_t ts = dtype == DICP_F32 ? 4 : 8;
-    if ((uintptr_t)workspace % 256 || (uintptr_t)pts % ts || (origin && (uintptr_t)origin % ts) || (uintptr_t)rows_out % 4 || ((uintptr_t)rows % 4))
-        return DICP_ERR_ALIGN;
+    const size_t ts = elem_size(dtype);
+    if (misaligned(workspace, 256) || misaligned(pts, ts) || misaligned(origin, ts) || misaligned(rows_out, 4) || misaligned(rows, 4)) return DICP_ERR_ALIGN;
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
     const int tpc = vox_tiles(m);
@@ -639,14 +638,13 @@ int dicp_voxel_count(int dtype, const void* pts, int c, const int32_t* rows, int
     int32_t* cinfo = (int32_t*)(ws + L.cinfo);
     int64_t* vlo = (int64_t*)(ws + L.vlo);
     begin_launch();
-#define DICP_VOX_FRONT(T) do { \
-        const T s0 = (T)sx, s1 = (T)sy, s2 = (T)sz; \
-        vox_bounds_kernel<T><<<g, BLOCK, 0, st>>>((const T*)pts, c, rows, N, m, tpc, s0, s1, s2, (const T*)origin, os, tmin, tmax, tcnt, tbad); \
-        vox_plan_kernel<<<N, BLOCK, 0, st>>>(N, tpc, tmin, tmax, tcnt, tbad, toff, cinfo, vlo); \
-        vox_keys_kernel<T><<<g, BLOCK, 0, st>>>((const T*)pts, c, rows, N, m, tpc, s0, s1, s2, (const T*)origin, os, toff, cinfo, vlo, key[0], idx[0]); \
-    } while (0)
-    if (dtype == DICP_F32) DICP_VOX_FRONT(float); else DICP_VOX_FRONT(double);
-#undef DICP_VOX_FRONT
+    with_scalar(dtype, [&](auto t) {
+        using T = decltype(t);
+        const T s0 = (T)sx, s1 = (T)sy, s2 = (T)sz;
+        vox_bounds_kernel<T><<<g, BLOCK, 0, st>>>((const T*)pts, c, rows, N, m, tpc, s0, s1, s2, (const T*)origin, os, tmin, tmax, tcnt, tbad);
+        vox_plan_kernel<<<N, BLOCK, 0, st>>>(N, tpc, tmin, tmax, tcnt, tbad, toff, cinfo, vlo);
+        vox_keys_kernel<T><<<g, BLOCK, 0, st>>>((const T*)pts, c, rows, N, m, tpc, s0, s1, s2, (const T*)origin, os, toff, cinfo, vlo, key[0], idx[0]);
+    });
     for (int p = 0; p < VOX_MAX_PASSES; ++p) {              // a cloud that needs fewer passes leaves these launches at once
         vox_hist_kernel<<<g, BLOCK, 0, st>>>(N, m, tpc, p, cinfo, key[p & 1], hist);
         vox_digit_scan_kernel<<<N, VOX_SCAN_THREADS, 0, st>>>(tpc, p, cinfo, hist);
@@ -672,8 +670,8 @@ int dicp_voxel_reduce(int dtype, const void* pts, int c, int N, int m, int M, co
     if (M < 0 || M > m) return DICP_ERR_SHAPE;
     const VoxLayout L = vox_layout(N, m);
     if (workspace_bytes < L.total) return DICP_ERR_SHAPE;
-    const size_t ts = dtype == DICP_F32 ? 4 : 8;
-    if ((uintptr_t)workspace % 256 || (uintptr_t)pts % ts || (uintptr_t)centroids % ts || (uintptr_t)counts % 4 || (uintptr_t)inverse % 8) return DICP_ERR_ALIGN;
+    const size_t ts = elem_size(dtype);
+    if (misaligned(workspace, 256) || misaligned(pts, ts) || misaligned(centroids, ts) || misaligned(counts, 4) || misaligned(inverse, 8)) return DICP_ERR_ALIGN;
     hipStream_t st = (hipStream_t)stream;
     const char* ws = (const char*)workspace;
     const size_t rows_total = (size_t)N * m;
@@ -696,12 +694,11 @@ int dicp_voxel_reduce(int dtype, const void* pts, int c, int N, int m, int M, co
     const size_t cap = vox_big_cap(N, m);
     const unsigned gb = (unsigned)(cap < (size_t)VOX_BIG_BLOCKS ? cap : (size_t)VOX_BIG_BLOCKS);
     begin_launch();
-#define DICP_VOX_REDUCE(T) do { \
-        vox_reduce_small_kernel<T><<<g, BLOCK, 0, st>>>((const T*)pts, c, N, m, M, bpc, cinfo, start, vidof, idx0, idx1, (T*)centroids, counts, inverse, big, bigcount); \
-        vox_reduce_big_kernel<T><<<gb, BLOCK, 0, st>>>((const T*)pts, c, m, M, cinfo, start, vidof, idx0, idx1, (T*)centroids, inverse, big, bigcount); \
-    } while (0)
-    if (dtype == DICP_F32) DICP_VOX_REDUCE(float); else DICP_VOX_REDUCE(double);
-#undef DICP_VOX_REDUCE
+    with_scalar(dtype, [&](auto t) {
+        using T = decltype(t);
+        vox_reduce_small_kernel<T><<<g, BLOCK, 0, st>>>((const T*)pts, c, N, m, M, bpc, cinfo, start, vidof, idx0, idx1, (T*)centroids, counts, inverse, big, bigcount);
+        vox_reduce_big_kernel<T><<<gb, BLOCK, 0, st>>>((const T*)pts, c, m, M, cinfo, start, vidof, idx0, idx1, (T*)centroids, inverse, big, bigcount);
+    });
     return launch_status();
 }
 
@@ -711,8 +708,8 @@ int dicp_voxel_backward(int dtype, const void* grad_centroids, const int64_t* in
     int rc = vox_check(dtype, N, m, c);
     if (rc) return rc;
     if (M < 0 || M > m) return DICP_ERR_SHAPE;
-    const size_t ts = dtype == DICP_F32 ? 4 : 8;
-    if ((uintptr_t)grad_centroids % ts || (uintptr_t)grad_pts % ts || (uintptr_t)counts % 4 || (uintptr_t)inverse % 8) return DICP_ERR_ALIGN;
+    const size_t ts = elem_size(dtype);
+    if (misaligned(grad_centroids, ts) || misaligned(grad_pts, ts) || misaligned(counts, 4) || misaligned(inverse, 8)) return DICP_ERR_ALIGN;
     const size_t rows_total = (size_t)N * m;
     const unsigned g = (unsigned)((rows_total + BLOCK - 1) / BLOCK);
     begin_launch();

@@ -15,7 +15,7 @@ import torch
 
 from . import _clouds, _lib
 from ._clouds import SLOT, CLOUD
-from ._ops import _DT, _p, _stream, _on, _workspace
+from ._ops import _DT, _p, _workspace
 
 T = 1024                                                    # threads of the resident workgroup (one per cloud)
 NR = {torch.float32: 16 * T, torch.float64: 8 * T}          # the largest cloud of the resident form: 16 / 8 rows a thread in registers
@@ -28,8 +28,7 @@ def _scatter(g, idx, shape):
     """the backward's one library call: zeros (N,n,c) with g's rows written at idx"""
     N, n, c, k = shape
     grad = torch.empty((N, n, c), dtype=g.dtype, device=g.device)
-    with _on(g.device):
-        _lib.check(_lib.load().dicp_fps_backward(_DT[g.dtype], _p(g), _p(idx), N, n, k, c, _p(grad), _stream()), "dicp_fps_backward")
+    _lib.call("dicp_fps_backward", g.device, _DT[g.dtype], _p(g), _p(idx), N, n, k, c, _p(grad))
     return grad
 
 
@@ -48,9 +47,7 @@ class _Fps(torch.autograd.Function):
         keff = torch.empty(N, dtype=torch.int32, device=dev)
         ws_bytes = lib.dicp_fps_workspace_bytes(dt, N, n, k, form)
         ws = _workspace(ws_bytes, dev) if ws_bytes else None
-        with _on(dev):
-            _lib.check(lib.dicp_fps_forward(dt, _p(pts), c, _p(rows), _p(start), N, n, k, form, _p(out), _p(idx), _p(dist), _p(keff),
-                                            _p(ws), ws_bytes, _stream()), "dicp_fps_forward")
+        _lib.call("dicp_fps_forward", dev, dt, _p(pts), c, _p(rows), _p(start), N, n, k, form, _p(out), _p(idx), _p(dist), _p(keff), _p(ws), ws_bytes)
         ctx.save_for_backward(idx)
         ctx.shape = (N, n, c, k)
         ctx.mark_non_differentiable(idx, keff, dist)

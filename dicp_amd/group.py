@@ -26,15 +26,15 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _clouds, _lib
-from ._clouds import ROW
+from ._clouds import ROW, K_MIN, K_MAX
 from ._ops import _DT, _p, _stream, _on
-from .knn import K_MIN, K_MAX
 
 
 def _dims(f, idx):
     return f.shape[0], idx.shape[1], f.shape[1], idx.shape[2], f.shape[2]            # N, n, m, k, C
 
 
+# (the forwards call the library directly: of their 30 us, _lib.call's lookup by name and extra frame are 0.5, profiles/r18_dispatch_host_time.txt)
 def _i64(idx):
     return 1 if idx.dtype == torch.int64 else 0
 
@@ -66,9 +66,7 @@ class _Group(torch.autograd.Function):
         g = g.contiguous()
         gf = torch.empty((N, m, C), dtype=g.dtype, device=g.device) if want_f else None
         gc = torch.empty((N, n, ctx.Cc), dtype=g.dtype, device=g.device) if want_c else None
-        with _on(g.device):
-            _lib.check(_lib.load().dicp_group_backward(_DT[g.dtype], _p(g), _p(idx), _i64(idx), _p(rows), ctx.Cc, N, n, m, k, C, _p(gf), _p(gc), _stream()),
-                       "dicp_group_backward")
+        _lib.call("dicp_group_backward", g.device, _DT[g.dtype], _p(g), _p(idx), _i64(idx), _p(rows), ctx.Cc, N, n, m, k, C, _p(gf), _p(gc))
         return gf, None, None, gc
 
 
@@ -98,9 +96,8 @@ class _Interpolate(torch.autograd.Function):
         g = g.contiguous()
         gf = torch.empty((N, m, C), dtype=g.dtype, device=g.device) if want_f else None
         gd = torch.empty((N, n, k), dtype=g.dtype, device=g.device) if want_d else None
-        with _on(g.device):
-            _lib.check(_lib.load().dicp_interpolate_backward(_DT[g.dtype], _p(g), _p(f), _p(out), _p(idx), _i64(idx), _p(rows), _p(d2), ctx.eps, N, n, m, k, C,
-                                                             _p(gf), _p(gd), _stream()), "dicp_interpolate_backward")
+        _lib.call("dicp_interpolate_backward", g.device, _DT[g.dtype], _p(g), _p(f), _p(out), _p(idx), _i64(idx), _p(rows), _p(d2), ctx.eps, N, n, m, k, C,
+                  _p(gf), _p(gd))
         return gf, None, gd, None, None
 
 
@@ -132,10 +129,8 @@ class _Pool(torch.autograd.Function):
         N, n, m, k, C = ctx.dims
         g = g.contiguous()
         gf = torch.empty((N, m, C), dtype=g.dtype, device=g.device)
-        with _on(g.device):
-            _lib.check(_lib.load().dicp_pool_backward(_DT[g.dtype], _p(g), _p(idx), _i64(idx), _p(rows), ctx.reduce,
-                                                      _p(amax) if ctx.reduce == _lib.POOL_MAX else None, _p(counts), N, n, m, k, C, _p(gf), _stream()),
-                       "dicp_pool_backward")
+        _lib.call("dicp_pool_backward", g.device, _DT[g.dtype], _p(g), _p(idx), _i64(idx), _p(rows), ctx.reduce,
+                  _p(amax) if ctx.reduce == _lib.POOL_MAX else None, _p(counts), N, n, m, k, C, _p(gf))
         return gf, None, None, None
 
 

@@ -10,17 +10,11 @@ Exact results on the GPU (libdicp_hip.so: dicp_knn_points / dicp_knn_points_back
 import torch
 
 from . import _clouds, _lib
-from ._clouds import ROW
-from ._ops import _DT, _p, _stream, _on
+from ._clouds import ROW, K_MIN, K_MAX, METHODS, _check_method      # noqa: F401  (METHODS: part of this module's interface)
+from ._grid import CellGrid, grid_knn
+from ._ops import _DT, _p
 
-K_MIN, K_MAX = 1, 32
 REDUCTIONS = ("mean", "sum", "none")
-METHODS = ("walk", "grid")
-
-
-def _check_method(method, what):
-    if not isinstance(method, str) or method not in METHODS:
-        raise ValueError('%s: method must be "walk" or "grid", got %r' % (what, method))
 
 
 class _Prepared:
@@ -38,12 +32,8 @@ class _Prepared:
         self.tgs4 = torch.empty((N, m_pad, 4), dtype=pts.dtype, device=dev)
         sb = lib.dicp_sweep_sort_scratch_bytes(dt, N, m_pad)
         scratch = torch.empty(sb, dtype=torch.uint8, device=dev) if sb else None
-        with _on(dev):
-            st = _stream()
-            _lib.check(lib.dicp_sweep_sort(dt, _p(pts), c, None, _p(rows), N, m, m_pad, _p(self.keys), _p(self.perm), 0, None, None,
-                                           _p(scratch), sb, st), "dicp_sweep_sort")
-            _lib.check(lib.dicp_sweep_build(dt, _p(pts), c, None, _p(rows), _p(self.perm), N, m, m_pad, _p(self.tgs4), None, 0, st),
-                       "dicp_sweep_build")
+        _lib.call("dicp_sweep_sort", dev, dt, _p(pts), c, None, _p(rows), N, m, m_pad, _p(self.keys), _p(self.perm), 0, None, None, _p(scratch), sb)
+        _lib.call("dicp_sweep_build", dev, dt, _p(pts), c, None, _p(rows), _p(self.perm), N, m, m_pad, _p(self.tgs4), None, 0)
 
 
 class _KnnPoints(torch.autograd.Function):
@@ -59,9 +49,8 @@ class _KnnPoints(torch.autograd.Function):
         d2 = torch.empty((N, n, k), dtype=x.dtype, device=x.device)
         idx = torch.empty((N, n, k), dtype=torch.int64, device=x.device)
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
-        with _on(x.device):
-            _lib.check(lib.dicp_knn_points(dt, _p(px.tgs4), _p(px.perm), _p(px.rows), n, _p(py.keys), _p(py.tgs4), _p(py.perm), _p(py.rows), m,
-                                           N, k, _p(d2), _p(idx), _p(ws), ws_bytes, None, _stream()), "dicp_knn_points")
+        _lib.call("dicp_knn_points", x.device, dt, _p(px.tgs4), _p(px.perm), _p(px.rows), n, _p(py.keys), _p(py.tgs4), _p(py.perm), _p(py.rows), m,
+                  N, k, _p(d2), _p(idx), _p(ws), ws_bytes, None)
         ctx.px, ctx.py, ctx.ws, ctx.k = px, py, ws, k
         ctx.mark_non_differentiable(idx)
         ctx.set_materialize_grads(False)
@@ -86,9 +75,8 @@ class _KnnPoints(torch.autograd.Function):
         g_bytes = lib.dicp_knn_points_workspace_bytes(dt, N, n, m, k, 1) if want_y else 0
         gws = torch.empty(g_bytes, dtype=torch.uint8, device=dev) if want_y else None
         g_d2 = g_d2.contiguous()
-        with _on(dev):
-            _lib.check(lib.dicp_knn_points_backward(dt, _p(g_d2), _p(px.tgs4), _p(px.perm), _p(px.rows), n, cx, _p(py.tgs4), _p(py.perm), m, cy,
-                                                    N, k, _p(ctx.ws), _p(gx), _p(gy), _p(gws), g_bytes, _stream()), "dicp_knn_points_backward")
+        _lib.call("dicp_knn_points_backward", dev, dt, _p(g_d2), _p(px.tgs4), _p(px.perm), _p(px.rows), n, cx, _p(py.tgs4), _p(py.perm), m, cy,
+                  N, k, _p(ctx.ws), _p(gx), _p(gy), _p(gws), g_bytes)
         return gx, gy, None, None, None
 
 
@@ -106,7 +94,7 @@ def knn_points(x, y, k=8, x_rows=None, y_rows=None, method="walk", _visited=None
         when they are CPU tensors.
     k: an int in [1, 32].
     method: "walk" (the default) searches along the x-sorted cloud; "grid" sorts y into a cell grid whose cell edge is chosen on the device
-        from y's own density (ball.CellGrid.by_density, about two rows per cell) and lets every query grow a box of cells until its k-th
+        from y's own density (CellGrid.by_density, about two rows per cell) and lets every query grow a box of cells until its k-th
         distance is proved final (dicp_knn_grid_build / dicp_knn_grid_query; the proof is csrc/dicp_gridknn.h).  Both are exact and return
         the same bits; they differ in speed only (README, "Nearest neighbours and Chamfer distance").
 
@@ -125,7 +113,6 @@ def knn_points(x, y, k=8, x_rows=None, y_rows=None, method="walk", _visited=None
     _check_method(method, "knn_points")
     form, on_cpu, lens, n, _, xb, yb, rx, ry = _clouds.pair(x, y, x_rows, y_rows, "knn_points")
     if method == "grid":
-        from .ball import CellGrid, grid_knn                # (ball.py imports this module)
         d2, idx = grid_knn(xb, yb, rx, CellGrid.by_density(yb.detach(), ry), k, _visited, _passes)
     else:
         px, py = _Prepared(xb.detach(), rx), _Prepared(yb.detach(), ry)
@@ -159,7 +146,6 @@ def chamfer_distance(x, y, x_rows=None, y_rows=None, reduction="mean", method="w
     _check_method(method, "chamfer_distance")
     form, on_cpu, _, n, m, xb, yb, rx, ry = _clouds.pair(x, y, x_rows, y_rows, "chamfer_distance")
     if method == "grid":
-        from .ball import CellGrid, grid_knn
         gx, gy = CellGrid.by_density(xb.detach(), rx), CellGrid.by_density(yb.detach(), ry)
         d_xy, d_yx = grid_knn(xb, yb, rx, gy, 1)[0][:, :n], grid_knn(yb, xb, ry, gx, 1)[0][:, :m]
     else:

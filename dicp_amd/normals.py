@@ -12,9 +12,8 @@ with method="grid"), with gradients back to the points:
 import torch
 
 from . import _clouds, _lib
-from ._clouds import ROW
-from ._ops import _DT, _p, _stream, _on, _workspace
-from .knn import _check_method
+from ._clouds import ROW, _check_method
+from ._ops import _DT, _p, _workspace
 
 K_MIN, K_MAX = 3, 32
 
@@ -41,13 +40,9 @@ class _Normals(torch.autograd.Function):
         nbr = buf[o_nbr: o_nbr + N * m * k * 8].view(torch.int64).view(N, m, k) if want_nbr else None
         ws = buf[o_ws:]
         per_cloud = int(vp is not None and vp.dim() == 2)
-        with _on(pts.device):
-            if grid:
-                _lib.check(lib.dicp_normals_grid_forward(dt, _p(pts), c, _p(rows), N, m, k, _p(vp), per_cloud, _p(nrm), _p(curv), _p(nbr),
-                                                         _p(ws), ws_bytes, _p(visited), _p(passes), _stream()), "dicp_normals_grid_forward")
-            else:
-                _lib.check(lib.dicp_normals_forward(dt, _p(pts), c, _p(rows), N, m, k, _p(vp), per_cloud,
-                                                    _p(nrm), _p(curv), _p(nbr), _p(ws), ws_bytes, None, _stream()), "dicp_normals_forward")
+        counters = (_p(visited), _p(passes)) if grid else (None,)        # (the walk's `walked` counter is not asked for)
+        _lib.call("dicp_normals_grid_forward" if grid else "dicp_normals_forward", pts.device, dt, _p(pts), c, _p(rows), N, m, k, _p(vp), per_cloud,
+                  _p(nrm), _p(curv), _p(nbr), _p(ws), ws_bytes, *counters)
         ctx.save_for_backward(rows, vp)
         ctx.ws = ws                                     # (a view of the outputs' allocation: kept off the saved-tensor version checks)
         ctx.shape, ctx.k, ctx.grid = (N, m, c), k, grid
@@ -75,13 +70,12 @@ class _Normals(torch.autograd.Function):
         g_nrm = g_nrm.contiguous() if g_nrm is not None else None
         g_curv = g_curv.contiguous() if g_curv is not None else None
         per_cloud = int(vp is not None and vp.dim() == 2)
-        with _on(ws.device):
-            if ctx.grid:
-                _lib.check(lib.dicp_normals_grid_backward(dt, _p(g_nrm), _p(g_curv), _p(vp), per_cloud, N, m, ctx.k, c,
-                                                          _p(ws), _p(grad), _p(gws), gws.numel(), _stream()), "dicp_normals_grid_backward")
-            else:
-                _lib.check(lib.dicp_normals_backward(dt, _p(g_nrm), _p(g_curv), _p(vp), per_cloud, _p(rows), N, m, ctx.k, c,
-                                                     _p(ws), _p(grad), _p(gws), gws.numel(), _stream()), "dicp_normals_backward")
+        if ctx.grid:
+            _lib.call("dicp_normals_grid_backward", ws.device, dt, _p(g_nrm), _p(g_curv), _p(vp), per_cloud, N, m, ctx.k, c,
+                      _p(ws), _p(grad), _p(gws), gws.numel())
+        else:
+            _lib.call("dicp_normals_backward", ws.device, dt, _p(g_nrm), _p(g_curv), _p(vp), per_cloud, _p(rows), N, m, ctx.k, c,
+                      _p(ws), _p(grad), _p(gws), gws.numel())
         return (grad,) + (None,) * 7
 
 

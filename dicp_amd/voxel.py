@@ -15,7 +15,7 @@ import torch
 
 from . import _clouds, _lib
 from ._clouds import ROW, CLOUD, VOXEL
-from ._ops import _DT, _p, _stream, _on, _workspace
+from ._ops import _DT, _p, _workspace
 
 _ERR = {1: "a voxel coordinate |floor((p - origin) / voxel_size)| reaches 2^62",
         2: "its voxel coordinates span more than 64 bits (w_x + w_y + w_z > 64)"}
@@ -33,21 +33,18 @@ class _Voxel(torch.autograd.Function):
         ws_bytes = lib.dicp_voxel_workspace_bytes(dt, N, m, c)
         ws = _workspace(ws_bytes, pts.device)
         info = torch.empty(N + 1, dtype=torch.int32, device=pts.device)
-        with _on(pts.device):
-            st = _stream()
-            _lib.check(lib.dicp_voxel_count(dt, _p(pts), c, _p(rows), N, m, size[0], size[1], size[2], _p(origin),
-                                            int(origin is not None and origin.dim() == 2), min_points, _p(info), _p(ws), ws_bytes, st),
-                       "dicp_voxel_count")
-            host = info.cpu()                                   # the one device -> host read of the call
-            err = int(host[N])
-            if err:
-                raise ValueError("voxel_downsample: cloud %d: %s" % ((err >> 2) - 1, _ERR.get(err & 3, "error %d" % err)))
-            M = int(host[:N].max())
-            cent = torch.empty((N, M, c), dtype=pts.dtype, device=pts.device)
-            counts = torch.empty((N, M), dtype=torch.int32, device=pts.device)
-            inverse = torch.empty((N, m), dtype=torch.int64, device=pts.device)
-            _lib.check(lib.dicp_voxel_reduce(dt, _p(pts), c, N, m, M, _p(ws), ws_bytes, _p(cent) if M else None, _p(counts) if M else None,
-                                             _p(inverse), st), "dicp_voxel_reduce")
+        _lib.call("dicp_voxel_count", pts.device, dt, _p(pts), c, _p(rows), N, m, size[0], size[1], size[2], _p(origin),
+                  int(origin is not None and origin.dim() == 2), min_points, _p(info), _p(ws), ws_bytes)
+        host = info.cpu()                                       # the one device -> host read of the call
+        err = int(host[N])
+        if err:
+            raise ValueError("voxel_downsample: cloud %d: %s" % ((err >> 2) - 1, _ERR.get(err & 3, "error %d" % err)))
+        M = int(host[:N].max())
+        cent = torch.empty((N, M, c), dtype=pts.dtype, device=pts.device)
+        counts = torch.empty((N, M), dtype=torch.int32, device=pts.device)
+        inverse = torch.empty((N, m), dtype=torch.int64, device=pts.device)
+        _lib.call("dicp_voxel_reduce", pts.device, dt, _p(pts), c, N, m, M, _p(ws), ws_bytes, _p(cent) if M else None, _p(counts) if M else None,
+                  _p(inverse))
         ctx.save_for_backward(inverse, counts)
         ctx.shape = (N, m, c, M)
         rows_dev, rows_host = info[:N], host[:N]
@@ -63,9 +60,7 @@ class _Voxel(torch.autograd.Function):
         N, m, c, M = ctx.shape
         g = g_cent.contiguous()
         grad = torch.empty((N, m, c), dtype=g.dtype, device=g.device)
-        with _on(g.device):
-            _lib.check(_lib.load().dicp_voxel_backward(_DT[g.dtype], _p(g) if M else None, _p(inverse), _p(counts) if M else None, N, m, M, c,
-                                                       _p(grad), _stream()), "dicp_voxel_backward")
+        _lib.call("dicp_voxel_backward", g.device, _DT[g.dtype], _p(g) if M else None, _p(inverse), _p(counts) if M else None, N, m, M, c, _p(grad))
         return grad, None, None, None, None
 
 
