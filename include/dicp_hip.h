@@ -1006,6 +1006,34 @@ int dicp_pool_forward(int dtype, const void* features, const void* idx, int idx6
 int dicp_pool_backward(int dtype, const void* grad_out, const void* idx, int idx64, const int32_t* rows, int reduce,
                        const int32_t* argmax, const int32_t* counts, int N, int n, int m, int k, int C, void* grad_features, void* stream);
 
+/* The inverted index of an index tensor (dicp_amd/group.py: invert_neighbors; csrc/inverse.hip, the rules: csrc/dicp_inverse.h) and the
+ * deterministic feature gradients that walk it.
+ *   Slot (i, s) of cloud b has the flat number q = i k + s and is live as above (0 <= idx < rows[b], one unsigned compare on the index's
+ *   full width).  offsets (N, m+1) int32: offsets[b, j] = the live slots of cloud b naming a row < j (so offsets[b, j] = the cloud's live
+ *   count L_b for every j >= rows[b]).  slots (N, n k) int32: slots[b, offsets[b, j] : offsets[b, j+1]] = the q of the live slots with
+ *   idx = j in ASCENDING q; slots[b, L_b:] = -1.  Both are fully defined and do not depend on scheduling: a stable radix sort of
+ *   (row, q) fed in ascending q.  n k < 2^31 per cloud (DICP_ERR_SHAPE).  workspace: dicp_invert_neighbors_workspace_bytes(N, n, m, k)
+ *   bytes (0 for a bad shape), 256-byte aligned, O(n k) per cloud whatever the in-degrees.  Nothing is read back; every launch is on `stream`.
+ * dicp_group_backward_det / dicp_pool_backward_det / dicp_interpolate_backward_det: grad_features (N,m,C) T of the three operators from
+ *   the pair (offsets, slots) that dicp_invert_neighbors gave for the same idx and rows.  Every element is stored once -- no zero fill,
+ *   no float atomics -- as the sum over its row's list in list order, in chunks of 64 list positions (csrc/dicp_inverse.h:
+ *   GROUP_DET_CHUNK): bit-reproducible.  The term of entry q = i k + s is what the atomic entry point adds for that slot: group
+ *   grad_out[b,i,s,c]; SUM grad_out[b,i,c]; MEAN grad_out[b,i,c] / T(counts[b,i]); MAX grad_out[b,i,c] when argmax[b,i,c] == j, once per
+ *   query however often it names j; interpolate w_s grad_out[b,i,c] with w recomputed from d2, nothing for a non-finite d2.  The other
+ *   gradients (grad_centers, grad_d2) come from the entry points above, called with grad_features = NULL.  The kernels stay in range
+ *   whatever offsets / slots hold (both ends of a list clamped to [0, n k]; an entry taken only when its q is in range and idx[q] names
+ *   the row); the values are defined only for dicp_invert_neighbors' output. */
+size_t dicp_invert_neighbors_workspace_bytes(int N, int n, int m, int k);
+int dicp_invert_neighbors(const void* idx, int idx64, const int32_t* rows, int N, int n, int m, int k,
+                          int32_t* offsets, int32_t* slots, void* workspace, size_t workspace_bytes, void* stream);
+int dicp_group_backward_det(int dtype, const void* grad_out, const void* idx, int idx64, const int32_t* rows, int N, int n, int m, int k, int C,
+                            const int32_t* offsets, const int32_t* slots, void* grad_features, void* stream);
+int dicp_pool_backward_det(int dtype, const void* grad_out, const void* idx, int idx64, const int32_t* rows, int reduce,
+                           const int32_t* argmax, const int32_t* counts, int N, int n, int m, int k, int C,
+                           const int32_t* offsets, const int32_t* slots, void* grad_features, void* stream);
+int dicp_interpolate_backward_det(int dtype, const void* grad_out, const void* idx, int idx64, const int32_t* rows, const void* d2, double eps,
+                                  int N, int n, int m, int k, int C, const int32_t* offsets, const int32_t* slots, void* grad_features, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
