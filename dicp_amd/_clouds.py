@@ -27,6 +27,12 @@ def _check_method(method, what):
         raise ValueError('%s: method must be "walk" or "grid", got %r' % (what, method))
 
 
+def _check_deterministic(deterministic, what):
+    """deterministic= of knn_points, ball_query and chamfer_distance (group.py's _inverse_arg has the same wording)"""
+    if not isinstance(deterministic, bool):
+        raise ValueError("%s: deterministic must be True or False, got %r" % (what, deterministic))
+
+
 def _check_points(t, name, what, min_cols=3):
     if not isinstance(t, torch.Tensor):
         _err(what, "%s must be a tensor, got %s" % (name, type(t).__name__))

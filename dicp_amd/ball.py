@@ -21,12 +21,12 @@ class _BallQuery(torch.autograd.Function):
     """(x (N,n,c), y (N,m,c)) -> (d2 (N,n,k), idx (N,n,k) int64, counts (N,n) int32) on y's grid: one library call per direction."""
 
     @staticmethod
-    def forward(ctx, x, y, grid, xkeys, xperm, k, visited):
-        return _forward(ctx, "dicp_ball_query", x, y, grid, xkeys, xperm, k, True, (visited,))
+    def forward(ctx, x, y, grid, xkeys, xperm, k, visited, det=False):
+        return _forward(ctx, "dicp_ball_query", x, y, grid, xkeys, xperm, k, True, (visited,), det)
 
     @staticmethod
     def backward(ctx, g_d2, _g_idx, _g_counts):
-        return _backward(ctx, g_d2, 7)
+        return _backward(ctx, g_d2, 8)
 
 
 def _err(msg):
@@ -52,7 +52,7 @@ def _check_radius(radius):
     return radius
 
 
-def ball_query(x, y, radius, k=16, x_rows=None, y_rows=None, return_counts=False, _visited=None):
+def ball_query(x, y, radius, k=16, x_rows=None, y_rows=None, return_counts=False, _visited=None, deterministic=False):
     """The rows of y within `radius` of every row of x: the nearest k of them, and optionally how many there are, exactly.
 
     x, y, x_rows, y_rows: as knn_points -- one cloud each (n, c) and (m, c); a padded batch each (N, n, c) and (N, m, c) with optional
@@ -62,6 +62,7 @@ def ball_query(x, y, radius, k=16, x_rows=None, y_rows=None, return_counts=False
         then r2 = radius_T * radius_T, rounded in T.  (A 0-d tensor that lives on the device is not read back, so it cannot be checked
         here: a value that is not a finite number > 0 in T gives every query count 0.)
     k: an int in [1, 32].
+    deterministic: a bool (anything else is a ValueError before any device work); see "Gradients".
 
     Definition: d2(i, j) is knn_points' own, (xx + yy) + zz with dx = y_j.x - x_i.x, xx = dx * dx (and so on) as separate roundings in T.
     The candidates of query i of cloud b are the rows j < y_rows[b] whose d2 is finite and d2 <= r2 -- the bound is inclusive.
@@ -76,8 +77,10 @@ def ball_query(x, y, radius, k=16, x_rows=None, y_rows=None, return_counts=False
 
     Gradients flow from d2 to x[..., :3] (sum_j 2 g_ij (x_i - y_idx)) and y[..., :3] (-sum 2 g_ij (x_i - y_l) over the entries with idx = l);
     other columns, pad rows and empty slots get zero whatever cotangent arrives there (NaN and inf included), and neither the choice of
-    neighbours nor counts carries any.  The forward and the x-gradient (written once per row) are bit-reproducible; the y-gradient sums
-    through float atomics, as knn_points' does, and is not, from run to run.
+    neighbours nor counts carries any.  The forward and the x-gradient (written once per row) are bit-reproducible.  The y-gradient is
+    by default added with float atomics, as knn_points' is, and its last bits can differ from run to run.  With deterministic=True it is
+    summed as knn_points describes -- per row of y over the row's list in the inverted index of idx, in chunks of 64 list positions,
+    stored once -- and is bit-reproducible too; the forward and the x-gradient are the default call's, bit for bit.
 
     y is sorted into a cell grid (CellGrid: the cell edge is the search half-width, a little above the radius, enlarged per cloud on the
     device where extent / radius would not fit a 64-bit key), the queries are processed in the order of its cells, and every query scans
@@ -85,6 +88,7 @@ def ball_query(x, y, radius, k=16, x_rows=None, y_rows=None, return_counts=False
     is kernels only.
     """
     _clouds._check_k(k, "ball_query", K_MIN, K_MAX)
+    _clouds._check_deterministic(deterministic, "ball_query")
     radius = _check_radius(radius)
     first = x[0] if isinstance(x, (list, tuple)) and x else x
     if isinstance(radius, float) and isinstance(first, torch.Tensor) and first.dtype in _DT:
@@ -98,5 +102,5 @@ def ball_query(x, y, radius, k=16, x_rows=None, y_rows=None, return_counts=False
         r_d = torch.full((1,), radius, dtype=xb.dtype, device=xb.device)         # (filled on the device, rounded to T: no copy)
     grid = CellGrid(yb.detach(), ry, r_d)
     xkeys, xperm = grid.order(xb.detach(), rx)
-    d2, idx, counts = _BallQuery.apply(xb, yb, grid, xkeys, xperm, k, _visited)
+    d2, idx, counts = _BallQuery.apply(xb, yb, grid, xkeys, xperm, k, _visited, deterministic)
     return _clouds.restore(form, on_cpu, n, lens, [(ROW, d2), (ROW, idx)] + ([(ROW, counts)] if return_counts else []))

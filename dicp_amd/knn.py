@@ -10,11 +10,12 @@ Exact results on the GPU (libdicp_hip.so: dicp_knn_points / dicp_knn_points_back
 import torch
 
 from . import _clouds, _lib
-from ._clouds import ROW, K_MIN, K_MAX, METHODS, _check_method      # noqa: F401  (METHODS: part of this module's interface)
-from ._grid import CellGrid, grid_knn
+from ._clouds import ROW, K_MIN, K_MAX, METHODS, _check_deterministic, _check_method      # noqa: F401  (METHODS: part of this module's interface)
+from ._grid import CellGrid, grad_y_det, grid_knn
 from ._ops import _DT, _p
 
 REDUCTIONS = ("mean", "sum", "none")
+DET_HUB = 4             # KNN_DET_HUB (csrc/dicp_knn_det.h): with deterministic=True a list of more than DET_HUB chunks of 64 entries is summed by a whole wave
 
 
 class _Prepared:
@@ -40,7 +41,7 @@ class _KnnPoints(torch.autograd.Function):
     """(x (N,n,c), y (N,m,c)) -> (d2 (N,n,k), idx (N,n,k) int64) on prepared clouds: one library call per direction on the current stream."""
 
     @staticmethod
-    def forward(ctx, x, y, px, py, k):
+    def forward(ctx, x, y, px, py, k, det=False):
         N, n, cx = px.shape
         m, cy = py.shape[1], py.shape[2]
         dt = _DT[x.dtype]
@@ -51,7 +52,9 @@ class _KnnPoints(torch.autograd.Function):
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
         _lib.call("dicp_knn_points", x.device, dt, _p(px.tgs4), _p(px.perm), _p(px.rows), n, _p(py.keys), _p(py.tgs4), _p(py.perm), _p(py.rows), m,
                   N, k, _p(d2), _p(idx), _p(ws), ws_bytes, None)
-        ctx.px, ctx.py, ctx.ws, ctx.k = px, py, ws, k
+        ctx.px, ctx.py, ctx.ws, ctx.k, ctx.det = px, py, ws, k, det
+        if det:                                             # the y-gradient walks the inverted index of idx over the caller's x and y
+            ctx.save_for_backward(x, y, idx)
         ctx.mark_non_differentiable(idx)
         ctx.set_materialize_grads(False)
         return d2, idx
@@ -59,33 +62,41 @@ class _KnnPoints(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_d2, _g_idx):
         if g_d2 is None:
-            return None, None, None, None, None
+            return (None,) * 6
         px, py, k = ctx.px, ctx.py, ctx.k
         N, n, cx = px.shape
         m, cy = py.shape[1], py.shape[2]
         want_x, want_y = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         if not (want_x or want_y):
-            return None, None, None, None, None
+            return (None,) * 6
         dtype = g_d2.dtype
         dt = _DT[dtype]
         lib = _lib.load()
         dev = g_d2.device
         gx = torch.empty((N, n, cx), dtype=dtype, device=dev) if want_x else None
+        if ctx.det:                                         # the x-gradient from the same kernel (grad_y = NULL), the y-gradient stored once
+            g_d2 = g_d2.contiguous()
+            if want_x:
+                _lib.call("dicp_knn_points_backward", dev, dt, _p(g_d2), _p(px.tgs4), _p(px.perm), _p(px.rows), n, cx, _p(py.tgs4), _p(py.perm), m, cy,
+                          N, k, _p(ctx.ws), _p(gx), None, None, 0)
+            x, y, idx = ctx.saved_tensors
+            gy = grad_y_det(g_d2, idx, py.rows, x, y) if want_y else None
+            return gx, gy, None, None, None, None
         gy = torch.empty((N, m, cy), dtype=dtype, device=dev) if want_y else None
         g_bytes = lib.dicp_knn_points_workspace_bytes(dt, N, n, m, k, 1) if want_y else 0
         gws = torch.empty(g_bytes, dtype=torch.uint8, device=dev) if want_y else None
         g_d2 = g_d2.contiguous()
         _lib.call("dicp_knn_points_backward", dev, dt, _p(g_d2), _p(px.tgs4), _p(px.perm), _p(px.rows), n, cx, _p(py.tgs4), _p(py.perm), m, cy,
                   N, k, _p(ctx.ws), _p(gx), _p(gy), _p(gws), g_bytes)
-        return gx, gy, None, None, None
+        return gx, gy, None, None, None, None
 
 
-def _search(xb, yb, px, py, k, n):
-    d2, idx = _KnnPoints.apply(xb, yb, px, py, k)
+def _search(xb, yb, px, py, k, n, det=False):
+    d2, idx = _KnnPoints.apply(xb, yb, px, py, k, det)
     return d2[:, :n], idx[:, :n]
 
 
-def knn_points(x, y, k=8, x_rows=None, y_rows=None, method="walk", _visited=None, _passes=None):
+def knn_points(x, y, k=8, x_rows=None, y_rows=None, method="walk", _visited=None, _passes=None, deterministic=False):
     """The k nearest rows of y for every row of x, exactly, with gradients of the squared distances.
 
     x, y: one cloud each (n, c) and (m, c); a padded batch each (N, n, c) and (N, m, c) with optional integer row counts x_rows / y_rows (N,);
@@ -97,6 +108,7 @@ def knn_points(x, y, k=8, x_rows=None, y_rows=None, method="walk", _visited=None
         from y's own density (CellGrid.by_density, about two rows per cell) and lets every query grow a box of cells until its k-th
         distance is proved final (dicp_knn_grid_build / dicp_knn_grid_query; the proof is csrc/dicp_gridknn.h).  Both are exact and return
         the same bits; they differ in speed only (README, "Nearest neighbours and Chamfer distance").
+    deterministic: a bool (anything else is a ValueError before any device work); see "Gradients".
 
     Definition: d2(i, j) = (xx + yy) + zz with dx = y_j.x - x_i.x, xx = dx * dx (and so on), in the inputs' dtype, as separate roundings.  The
     candidates of query i of cloud b are the rows j < y_rows[b] whose d2 is finite; the result is the first k_eff = min(k, #candidates) of
@@ -106,17 +118,26 @@ def knn_points(x, y, k=8, x_rows=None, y_rows=None, method="walk", _visited=None
 
     Gradients flow from d2 to x[..., :3] (sum_j 2 g_ij (x_i - y_idx)) and y[..., :3] (-sum 2 g_ij (x_i - y_l) over the entries with idx = l);
     other columns, pad rows and idx = -1 entries get zero, and the choice of neighbours gets none.  The forward and the x-gradient are
-    bit-reproducible; the y-gradient sums through float atomics and is not, from run to run.  With method="grid" the backward is
-    ball_query's (dicp_ball_query_backward), with the same properties.
+    bit-reproducible.  The y-gradient is by default added with float atomics: the order, and so the last bits, can differ from run to
+    run.  With method="grid" the backward is ball_query's (dicp_ball_query_backward), with the same properties.
+
+    With deterministic=True the forward and the x-gradient are the default call's, bit for bit, and the y-gradient is summed per row l
+    of y over the row's list in the inverted index of the returned idx (group.invert_neighbors, built once inside the backward and only
+    when y needs a gradient: the entries with idx = l in ascending i k + s), in chunks of 64 list positions -- each chunk from +0 by
+    plain additions, the chunks' partials added in order to a total that starts at +0, a single chunk as it is.  A term is
+    -(2 g_is)(x_i - y_l) per coordinate, formed in float64 and rounded once to the inputs' dtype (the value the atomics add); an entry
+    whose cotangent is 0 has no term.  Every element is stored once -- no zero fill, no atomics: bit-reproducible, and the same bytes
+    under "walk" and "grid" (dicp_knn_backward_y_det).
     """
     _clouds._check_k(k, "knn_points", K_MIN, K_MAX)
     _check_method(method, "knn_points")
+    _check_deterministic(deterministic, "knn_points")
     form, on_cpu, lens, n, _, xb, yb, rx, ry = _clouds.pair(x, y, x_rows, y_rows, "knn_points")
     if method == "grid":
-        d2, idx = grid_knn(xb, yb, rx, CellGrid.by_density(yb.detach(), ry), k, _visited, _passes)
+        d2, idx = grid_knn(xb, yb, rx, CellGrid.by_density(yb.detach(), ry), k, _visited, _passes, deterministic)
     else:
         px, py = _Prepared(xb.detach(), rx), _Prepared(yb.detach(), ry)
-        d2, idx = _KnnPoints.apply(xb, yb, px, py, k)
+        d2, idx = _KnnPoints.apply(xb, yb, px, py, k, deterministic)
     return _clouds.restore(form, on_cpu, n, lens, [(ROW, d2), (ROW, idx)])
 
 
@@ -130,7 +151,7 @@ def _direction(d2, rows, n):
     return s / cnt.clamp(min=1).to(d2.dtype)
 
 
-def chamfer_distance(x, y, x_rows=None, y_rows=None, reduction="mean", method="walk"):
+def chamfer_distance(x, y, x_rows=None, y_rows=None, reduction="mean", method="walk", deterministic=False):
     """Chamfer distance between two clouds: for cloud b, mean_{i < n_b} d2(x_i, NN_y(x_i)) + mean_{j < m_b} d2(y_j, NN_x(y_j)).
 
     x, y and the row counts: as knn_points.  d2 as knn_points defines it (squared, in the inputs' dtype).  A direction whose query side is
@@ -138,20 +159,25 @@ def chamfer_distance(x, y, x_rows=None, y_rows=None, reduction="mean", method="w
     reduction: "mean" or "sum" over the batch (a scalar), or "none" ((N,), one value per cloud; (1,) for single clouds).
 
     Each cloud is sorted once and searched in both directions (two k = 1 searches of knn_points); gradients flow to x[..., :3] and y[..., :3]
-    as knn_points describes, and through the same float atomics.
+    as knn_points describes: by default through the same float atomics.
     method: as knn_points.  "grid" builds the cell grid of each cloud once and searches each direction on the other cloud's grid.
+    deterministic: a bool, as knn_points.  True makes both searches deterministic: each cloud's gradient is then the sum of two tensors
+        that were each written once (its x-gradient as the query side of one search, its y-gradient in the order of summation knn_points
+        describes as the target side of the other), and a two-term float add is commutative: the gradients are bit-reproducible
+        whatever order autograd adds them in.
     """
     if not isinstance(reduction, str) or reduction not in REDUCTIONS:
         raise ValueError("chamfer_distance: reduction must be one of %s, got %r" % (", ".join(REDUCTIONS), reduction))
     _check_method(method, "chamfer_distance")
+    _check_deterministic(deterministic, "chamfer_distance")
     form, on_cpu, _, n, m, xb, yb, rx, ry = _clouds.pair(x, y, x_rows, y_rows, "chamfer_distance")
     if method == "grid":
         gx, gy = CellGrid.by_density(xb.detach(), rx), CellGrid.by_density(yb.detach(), ry)
-        d_xy, d_yx = grid_knn(xb, yb, rx, gy, 1)[0][:, :n], grid_knn(yb, xb, ry, gx, 1)[0][:, :m]
+        d_xy, d_yx = grid_knn(xb, yb, rx, gy, 1, det=deterministic)[0][:, :n], grid_knn(yb, xb, ry, gx, 1, det=deterministic)[0][:, :m]
     else:
         px, py = _Prepared(xb.detach(), rx), _Prepared(yb.detach(), ry)
-        d_xy, _ = _search(xb, yb, px, py, 1, n)
-        d_yx, _ = _search(yb, xb, py, px, 1, m)
+        d_xy, _ = _search(xb, yb, px, py, 1, n, deterministic)
+        d_yx, _ = _search(yb, xb, py, px, 1, m, deterministic)
     per = _direction(d_xy, rx, n) + _direction(d_yx, ry, m)
     out = per if reduction == "none" else (per.mean() if reduction == "mean" else per.sum())
     return out.cpu() if on_cpu else out

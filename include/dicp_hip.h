@@ -1034,6 +1034,21 @@ int dicp_pool_backward_det(int dtype, const void* grad_out, const void* idx, int
 int dicp_interpolate_backward_det(int dtype, const void* grad_out, const void* idx, int idx64, const int32_t* rows, const void* d2, double eps,
                                   int N, int n, int m, int k, int C, const int32_t* offsets, const int32_t* slots, void* grad_features, void* stream);
 
+/* The deterministic y-gradient of the neighbour searches (knn_points / ball_query / chamfer_distance with deterministic=True;
+ * csrc/knn_det.hip, the rules: csrc/dicp_knn_det.h): grad_y (N,m,cy) T of dicp_knn_points_backward / dicp_ball_query_backward from the
+ * pair (offsets, slots) that dicp_invert_neighbors gave for the searches' PUBLIC idx output (N,n,k) int64 -- original row numbers of y,
+ * -1 in empty slots -- with rows = y_rows and m.  g_d2 (N,n,k), x (N,n,cx), y (N,m,cy) are the caller's own arrays, not the sorted
+ * copies, so one entry point serves the walk, the grid and ball_query.  Row l < y_rows[b] receives, per component a < 3, the sum over
+ * its list in list order of t_a = (T)(-(2.0 (double)g) ((double)x[b,i,a] - (double)y[b,l,a])), g = g_d2[b,i,s] -- the value the atomic
+ * kernels add, rounded once to T; an entry with g == 0 has no term -- in chunks of 64 list positions, each from +0, the partials added
+ * in order to a total that starts at +0, a single chunk as it is.  Columns 3..cy-1, rows at or past y_rows[b] and rows nobody names get
+ * 0.  Every element of grad_y is stored exactly once: no zero fill, no float atomics, no workspace; bit-reproducible.  A list longer
+ * than KNN_DET_HUB chunks is summed by a whole wave in the same order.  The x-gradient comes from the entry points above, called with
+ * grad_y = NULL.  1 <= k <= 32, cx, cy >= 3, n k < 2^31 per cloud (DICP_ERR_SHAPE).  The kernel stays in range whatever offsets /
+ * slots hold, as the feature gradients do. */
+int dicp_knn_backward_y_det(int dtype, const void* g_d2, const int64_t* idx, const int32_t* y_rows, const void* x, int cx, int n,
+                            const void* y, int cy, int m, int N, int k, const int32_t* offsets, const int32_t* slots, void* grad_y, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
