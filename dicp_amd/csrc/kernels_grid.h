@@ -11,18 +11,12 @@
 #include "dicp_common.h"
 #include "dicp_ball.h"
 #include "dicp_gridknn.h"
+#include "kernels_grid_plan.h"
 
 namespace {
 
 constexpr int BALL_KMAX = 32;
 constexpr int BALL_CHUNK = 2048;                        // pairs a workgroup sorts in LDS: 24 KiB
-
-inline int ball_slots(int m) { int p = 2; while (p < m) p <<= 1; return p; }
-
-template <typename T>
-__device__ __forceinline__ const BallPlan<T>& plan_of(const void* plans, int b) {
-    return *(const BallPlan<T>*)((const char*)plans + (size_t)b * BALL_PLAN_BYTES);
-}
 
 // The per-axis bounds mn / mx and the number cnt of the live rows (j < rows[b], three finite coordinates) of cloud b = blockIdx.x, one
 // workgroup of BLOCK threads per cloud; the result is thread 0's (the others hold partial values)
@@ -145,13 +139,6 @@ __global__ __launch_bounds__(BLOCK) void ball_pack_kernel(const T* __restrict__ 
         }
         rows4[e] = v;
     }
-}
-
-int ball_check(int dtype, int N, int m) {
-    if (bad_dtype(dtype)) return DICP_ERR_DTYPE;
-    if (N <= 0 || m <= 0 || m > (1 << 30)) return DICP_ERR_SHAPE;
-    if ((size_t)N * ball_slots(m) > ((size_t)1 << 40)) return DICP_ERR_SHAPE;
-    return 0;
 }
 
 // The arguments dicp_ball_query and dicp_knn_grid_query have in common, checked in the order that decides the status of a bad call

@@ -2,7 +2,8 @@
 
 `ICP(icp_type='pt2pl')` takes target rows (m, 6) = xyz + unit normal.  `estimate_normals` computes those normals from the points
 alone, on the GPU (libdicp_hip.so: dicp_normals_forward / dicp_normals_backward, or dicp_normals_grid_forward / dicp_normals_grid_backward
-with method="grid"), with gradients back to the points:
+with method="grid"), with gradients back to the points -- summed with float atomics, or with deterministic=True stored once per element
+from the inverted index of the neighbours (dicp_normals_backward_records / dicp_normals_gather_det):
 
     from dicp_amd.normals import estimate_normals
     nrm = estimate_normals(pts, k=16)
@@ -14,6 +15,9 @@ import torch
 from . import _clouds, _lib
 from ._clouds import ROW, _check_method
 from ._ops import _DT, _p, _workspace
+from .group import _invert
+
+REC = 13                # NRM_REC (csrc/dicp_normals_det.h): the doubles of a row's record, G6[0:6], mu[6:9], p[9:12], f[12]
 
 K_MIN, K_MAX = 3, 32
 
@@ -21,10 +25,11 @@ K_MIN, K_MAX = 3, 32
 class _Normals(torch.autograd.Function):
     """(N,m,c) points -> (normals (N,m,3), curvature (N,m), neighbours (N,m,k) int64 or None): one library call per direction on the current
     stream, into one allocation per direction.  grid: the neighbours from the cloud's cell grid (dicp_normals_grid_*) instead of the
-    x-sorted walk; visited / passes: its optional (N,) int64 counters."""
+    x-sorted walk; visited / passes: its optional (N,) int64 counters.  det: the backward stores every element once (_backward_det); records:
+    an optional list that backward appends its (records, nbr_o) to."""
 
     @staticmethod
-    def forward(ctx, pts, rows, vp, k, want_nbr, grid, visited, passes):
+    def forward(ctx, pts, rows, vp, k, want_nbr, grid, visited, passes, det, records):
         N, m, c = pts.shape
         dt = _DT[pts.dtype]
         lib = _lib.load()
@@ -45,7 +50,7 @@ class _Normals(torch.autograd.Function):
                   _p(nrm), _p(curv), _p(nbr), _p(ws), ws_bytes, *counters)
         ctx.save_for_backward(rows, vp)
         ctx.ws = ws                                     # (a view of the outputs' allocation: kept off the saved-tensor version checks)
-        ctx.shape, ctx.k, ctx.grid = (N, m, c), k, grid
+        ctx.shape, ctx.k, ctx.grid, ctx.det, ctx.records = (N, m, c), k, grid, det, records
         ctx.set_materialize_grads(False)
         if nbr is not None:
             ctx.mark_non_differentiable(nbr)
@@ -54,12 +59,14 @@ class _Normals(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_nrm, g_curv, _g_nbr):
         if g_nrm is None and g_curv is None:
-            return (None,) * 8
+            return (None,) * 10
         rows, vp = ctx.saved_tensors
         ws = ctx.ws
         N, m, c = ctx.shape
         dtype = g_nrm.dtype if g_nrm is not None else g_curv.dtype
         dt = _DT[dtype]
+        if ctx.det:
+            return (_backward_det(ctx, g_nrm, g_curv, rows, vp, dtype),) + (None,) * 9
         lib = _lib.load()
         ts = torch.empty((), dtype=dtype).element_size()
         g_bytes = (lib.dicp_normals_grid_workspace_bytes if ctx.grid else lib.dicp_normals_workspace_bytes)(dt, N, m, ctx.k, c, 1)
@@ -76,11 +83,32 @@ class _Normals(torch.autograd.Function):
         else:
             _lib.call("dicp_normals_backward", ws.device, dt, _p(g_nrm), _p(g_curv), _p(vp), per_cloud, _p(rows), N, m, ctx.k, c,
                       _p(ws), _p(grad), _p(gws), gws.numel())
-        return (grad,) + (None,) * 7
+        return (grad,) + (None,) * 9
+
+
+def _backward_det(ctx, g_nrm, g_curv, rows, vp, dtype):
+    """The points' gradient with deterministic=True -> (N,m,c): the records pass (every query's G6, mu, p, f and its neighbours as original
+    rows, at its original row), the inverted index of those neighbours -- built here, once, and only because the points need a gradient
+    -- and the gather, which stores every element once.  Allocations and launches on the current stream only."""
+    ws = ctx.ws
+    N, m, c = ctx.shape
+    dt = _DT[dtype]
+    g_nrm = g_nrm.contiguous() if g_nrm is not None else None
+    g_curv = g_curv.contiguous() if g_curv is not None else None
+    records = torch.empty((N, m, REC), dtype=torch.float64, device=ws.device)
+    nbr_o = torch.empty((N, m, ctx.k), dtype=torch.int32, device=ws.device)
+    _lib.call("dicp_normals_backward_records", ws.device, dt, int(ctx.grid), _p(g_nrm), _p(g_curv), _p(vp), int(vp is not None and vp.dim() == 2),
+              _p(rows), N, m, ctx.k, c, _p(ws), ws.numel(), _p(records), _p(nbr_o))
+    off, slots = _invert(nbr_o, rows, m)
+    grad = torch.empty((N, m, c), dtype=dtype, device=ws.device)
+    _lib.call("dicp_normals_gather_det", ws.device, dt, _p(records), _p(nbr_o), 0, _p(rows), N, m, ctx.k, c, _p(off), _p(slots), _p(grad))
+    if ctx.records is not None:
+        ctx.records.append((records, nbr_o))
+    return grad
 
 
 def estimate_normals(points, k=16, viewpoint=None, rows=None, return_curvature=False, return_neighbors=False, method="walk",
-                     _visited=None, _passes=None):
+                     deterministic=False, _visited=None, _passes=None, _records=None):
     """Unit surface normals of every point from its k nearest neighbours in its own cloud.
 
     points: (m, c), (N, m, c) with c >= 3 (columns 0:3 are used), or a list of (m_b, c); float32 or float64.  CPU tensors are computed on the
@@ -95,6 +123,7 @@ def estimate_normals(points, k=16, viewpoint=None, rows=None, return_curvature=F
         knn_points' rule: the candidates of point i are the rows below the row count with three finite coordinates whose d2 to i is
         finite, and k_eff(i) = min(k, their number); a row with a non-finite coordinate is nobody's neighbour and gets a zero normal,
         zero curvature, -1 neighbours and no gradient; k_eff(i) < 3 gives the zero normal.  Nothing is read back from the device.
+    deterministic: a bool (anything else is a ValueError before any device work); see "Gradients".
 
     Definition (what the tests pin): the neighbours of point i are the k_eff = min(k, rows_b) rows of its cloud first in (d2, index) order, i itself
     among them, d2 = (dx*dx + dy*dy) + dz*dz; C = (1/k_eff) sum (q_j - mu)(q_j - mu)^T with q_j = p_j - p_i and mu = mean q; the normal is C's
@@ -108,10 +137,21 @@ def estimate_normals(points, k=16, viewpoint=None, rows=None, return_curvature=F
     Gradients flow to points[..., :3] (zero for the other columns); the viewpoint only picks a sign and gets none, nor do the neighbour choice
     and the sign (piecewise constant).  A point whose two smallest eigenvalues are not separated -- lam1 - lam0 <= tau (lam0 + lam1 + lam2),
     tau = 1e-6 for float32 and 1e-12 for float64 -- contributes a zero gradient instead of inf or NaN: its normal is not a function of the
-    points there.  The backward sums through float atomics, so its result is not bit-reproducible from run to run.
+    points there; so does a point with k_eff < 3 or whose cotangents are all zero.  By default the terms are added with float atomics, and
+    the last bits can differ from run to run.  With deterministic=True the forward is the default call's, bit for bit, and row j receives,
+    per component, the sum over its list in the inverted index of the neighbour tensor (group.invert_neighbors(nbr, m, rows=rows): the
+    slots q = i k + o with nbr[i, o] = j, in ascending q; built once inside the backward and only when the points need a gradient) of
+    t_a = (T)(f ((G_a0 d_0 + G_a1 d_1) + G_a2 d_2)), d_c = ((double)y_c - (double)p_c) - mu_c, f = 2 / k_eff, with y row j's coordinates
+    and p, mu, G = dL/dC query i's: one rounding per operation in double, one to the points' dtype T.  An entry whose query contributes
+    nothing has no term; its position still counts.  The list is summed in chunks of group.DET_CHUNK = 64 positions, each from +0 by plain
+    additions in T, the partials added in order to a total that starts at +0, a list of at most one chunk giving its partial itself.
+    Every element is stored exactly once (no zero fill, no atomics): the result is bit-reproducible, the same bytes under "walk" and
+    "grid" wherever the walk is defined, and within rounding of the default's (a term may differ from the atomic path's in the last bit
+    of the double before it is rounded to T).
     """
     _clouds._check_k(k, "estimate_normals", K_MIN, K_MAX)
     _check_method(method, "estimate_normals")
+    _clouds._check_deterministic(deterministic, "estimate_normals")
     form, batch, rows, lens = _clouds.check(points, rows, "estimate_normals", flat_rows=True)
     N, m = batch.shape[0], batch.shape[1]
     vp = None
@@ -122,7 +162,7 @@ def estimate_normals(points, k=16, viewpoint=None, rows=None, return_curvature=F
 
     on_cpu, x, rows_d = _clouds.place(batch, rows)
     vp_d = vp.detach().to(device=x.device, dtype=x.dtype).contiguous() if vp is not None else None
-    nrm, curv, nbr = _Normals.apply(x, rows_d, vp_d, k, bool(return_neighbors), method == "grid", _visited, _passes)
+    nrm, curv, nbr = _Normals.apply(x, rows_d, vp_d, k, bool(return_neighbors), method == "grid", _visited, _passes, deterministic, _records)
     outs = [(ROW, nrm)] + ([(ROW, curv)] if return_curvature else []) + ([(ROW, nbr)] if return_neighbors else [])
     outs = _clouds.restore(form, on_cpu, m, lens, outs)
     return outs[0] if len(outs) == 1 else outs

@@ -1049,6 +1049,26 @@ int dicp_interpolate_backward_det(int dtype, const void* grad_out, const void* i
 int dicp_knn_backward_y_det(int dtype, const void* g_d2, const int64_t* idx, const int32_t* y_rows, const void* x, int cx, int n,
                             const void* y, int cy, int m, int N, int k, const int32_t* offsets, const int32_t* slots, void* grad_y, void* stream);
 
+/* The deterministic backward of the surface normals (estimate_normals with deterministic=True; csrc/normals_det.hip, the rule per element:
+ * csrc/dicp_normals_det.h): two passes around the inverted index (dicp_invert_neighbors) of the neighbour tensor.
+ * dicp_normals_backward_records: from the forward's workspace (grid = 0: dicp_normals_forward's, 1: dicp_normals_grid_forward's; its size in
+ *   fwd_workspace_bytes) and the cotangents g_normals (N,m,3) / g_curvature (N,m) of dtype T (either may be NULL), with the forward's viewpoint,
+ *   rows, k and c: records (N,m,13) double -- per ORIGINAL row G6[0..6) = dL/dC symmetrised, mu[0..3), p[0..3) the row's coordinates, f = 2 / k_eff,
+ *   or f = 0 (and G6 = mu = 0) for a query that contributes nothing: k_eff < 3, both cotangents zero or absent, eigenvalues not separated, zero trace;
+ *   all zeros for a row that takes no part -- and nbr_o (N,m,k) int32: the neighbours as original rows, -1 where none.  Both are written in full.
+ * dicp_normals_gather_det: grad_pts (N,m,c) T, every element stored once (columns 3:c and rows at or past rows[b]: +0; no zero fill, no atomics).
+ *   idx (N,m,k) int32 (idx64 = 0) or int64 (1): the neighbours as original rows; offsets (N,m+1) / slots (N,m*k): dicp_invert_neighbors of idx with
+ *   n = m and the same rows.  Row j receives per component the sum over its list (the slots q = i k + o with idx = j, ascending q) of
+ *   t_a = (T)(f ((G_a0 d_0 + G_a1 d_1) + G_a2 d_2)), d = ((double)y - p) - mu, y = records[j, 9:12] and G, mu, p, f = records[i]: one rounding per
+ *   operation in double, one to T; an entry whose query has f = 0 has no term.  The order is dicp_group_backward_det's: chunks of 64 list
+ *   positions, each summed from +0 in T, the partials added in order to a total that starts at +0, a single chunk giving its partial itself.
+ *   Nothing outside the arrays is read whatever offsets / slots / idx hold. */
+int dicp_normals_backward_records(int dtype, int grid, const void* g_normals, const void* g_curvature, const void* viewpoint, int vp_per_cloud,
+                                  const int32_t* rows, int N, int m, int k, int c, const void* fwd_workspace, size_t fwd_workspace_bytes,
+                                  double* records, int32_t* nbr_o, void* stream);
+int dicp_normals_gather_det(int dtype, const double* records, const void* idx, int idx64, const int32_t* rows, int N, int m, int k, int c,
+                            const int32_t* offsets, const int32_t* slots, void* grad_pts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
