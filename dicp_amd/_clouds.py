@@ -144,6 +144,41 @@ def check_slots(t, what, name, like, integer, k_lo, k_hi):
     return batch, lens
 
 
+def check_mask(t, what, name, like):
+    """A keep-mask, one torch.bool per row, in the form of the points it goes with: (m,), (N, m) or a list of (m_b,) -> batch (N, m) bool
+    (a list is padded with False); ValueError for anything invalid.
+
+    like: the checked form, batch and list lengths (form, batch, lens) of the points: the same form, cloud count, row counts and device."""
+    form, other, lens = like
+    is_list = isinstance(t, (list, tuple))
+    items = list(t) if is_list else [t]
+    if is_list and not items:
+        _err(what, "%s is an empty list" % name)
+    for i, c in enumerate(items):
+        nm = "%s[%d]" % (name, i) if is_list else name
+        if not isinstance(c, torch.Tensor):
+            _err(what, "%s must be a tensor, got %s" % (nm, type(c).__name__))
+        if c.dtype != torch.bool:
+            _err(what, "%s must be torch.bool, got %s" % (nm, c.dtype))
+        if is_list and c.dim() != 1:
+            _err(what, "%s must be (m_b,), got shape %s" % (nm, tuple(c.shape)))
+        if c.device != other.device:
+            _err(what, "%s and the points must be on one device, got %s and %s" % (nm, c.device, other.device))
+    if not is_list and t.dim() not in (1, 2):
+        _err(what, "%s must be (m,), (N, m) or a list of (m_b,), got shape %s" % (name, tuple(t.shape)))
+    mine = "list" if is_list else ("single" if t.dim() == 1 else "batch")
+    if mine != form:
+        _err(what, "%s must have the form of the points (single clouds, padded batches or lists), got %s and %s" % (name, mine, form))
+    if is_list:
+        if [c.shape[0] for c in items] != list(lens):
+            _err(what, "%s must hold one entry per row of every cloud, got lengths %s for clouds of %s rows" % (name, [c.shape[0] for c in items], list(lens)))
+        return torch.nn.utils.rnn.pad_sequence(items, batch_first=True, padding_value=False)
+    batch = t.unsqueeze(0) if t.dim() == 1 else t
+    if tuple(batch.shape) != tuple(other.shape[:2]):
+        _err(what, "%s must hold one entry per row, shape %s, got %s" % (name, tuple(other.shape[1:2] if form == "single" else other.shape[:2]), tuple(t.shape)))
+    return batch
+
+
 def place(batch, rows, xyz=False):
     """A checked batch and its rows on the compute device -> (on_cpu, batch (N,m',c') contiguous, rows (N,) int32 or None).
 

@@ -1069,6 +1069,33 @@ int dicp_normals_backward_records(int dtype, int grid, const void* g_normals, co
 int dicp_normals_gather_det(int dtype, const double* records, const void* idx, int idx64, const int32_t* rows, int N, int m, int k, int c,
                             const int32_t* offsets, const int32_t* slots, void* grad_pts, void* stream);
 
+/* Outlier removal (dicp_amd/filter.py; csrc/filter.hip, the rules: csrc/dicp_filter.h).
+ * dicp_select_rows: the stable compaction of a padded batch by a mask.  pts (N,m,c) T, c >= 1; mask (N,m) bytes (0 = drop); rows: optional (N)
+ *   row counts as tgt_rows.  Row r of cloud b is kept when r < rows[b] and mask[b,r] != 0; the values are never looked at.  Written: out (N,m,c) T
+ *   -- the kept rows in their order, all c columns bit for bit, zero at and past rows_out[b]; rows_out (N) int32; index (N,m) int64, optional --
+ *   the input row of every output row, -1 past rows_out[b]; pos (N,m) int32, optional -- the output row of every input row, -1 for a dropped one.
+ *   Every element is stored exactly once (no fill), in three launches: per-tile counts, a per-cloud scan, the move.  out must not be pts.
+ *   workspace: dicp_select_workspace_bytes(N, m) bytes (0 for bad arguments), 256-byte aligned.
+ * dicp_select_rows_backward: grad_pts (N,m,c) T = grad_out[b, pos[b,i]], 0 where pos is negative (or not a row): every element stored once, no
+ *   atomics.
+ * dicp_outlier_stats: the decision of the statistical filter from a cloud's (k + 1)-slot search against itself, d2 (N,m,k+1) T and idx
+ *   (N,m,k+1) int64 as dicp_knn_points' callers hold them (original rows, -1 in empty slots), 1 <= k <= 31.  Everything in double.  Row
+ *   i < rows[b] walks its slots in order, skips those with idx = i or idx < 0 and takes the first k that remain, cnt of them:
+ *   mean_distance[b,i] = (the sum of sqrt(d2) in slot order from +0) / cnt, +inf for cnt = 0 and for rows at or past rows[b] -- such a row
+ *   is invalid, takes no part below and is dropped.  Over the cloud's V valid rows in row order, with sum64 = sequential from +0 for at
+ *   most 64 values, otherwise sum64 of the partials of consecutive chunks of 64: mean = sum64(md) / V, var = sum64(t t) / (V - 1) with
+ *   t = md - mean and the square rounded before it is added, std = sqrt(var) (0 for V < 2), thr = mean + (std_ratio std) with the product
+ *   rounded first.  Written: mean_distance (N,m) double, stats (N,3) double = mean, std, thr (V = 0: NaN, 0, NaN), mask (N,m) bytes = 1 where
+ *   the row is valid and md <= thr.  std_ratio finite and >= 0 (DICP_ERR_SHAPE).  No float atomics: bit-reproducible.
+ *   workspace: dicp_outlier_workspace_bytes(N, m) bytes (0 for bad arguments), 256-byte aligned. */
+size_t dicp_select_workspace_bytes(int N, int m);
+int dicp_select_rows(int dtype, const void* pts, int c, const uint8_t* mask, const int32_t* rows, int N, int m, void* out, int32_t* rows_out,
+                     int64_t* index, int32_t* pos, void* workspace, size_t workspace_bytes, void* stream);
+int dicp_select_rows_backward(int dtype, const void* grad_out, const int32_t* pos, int N, int m, int c, void* grad_pts, void* stream);
+size_t dicp_outlier_workspace_bytes(int N, int m);
+int dicp_outlier_stats(int dtype, const void* d2, const int64_t* idx, const int32_t* rows, int N, int m, int k, double std_ratio,
+                       double* mean_distance, double* stats, uint8_t* mask, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
