@@ -561,6 +561,9 @@ template <typename T> struct SkipArgs {
     double eps;
     int k;                   // this iteration (delta_k - 6 j = the step of iteration k - j)
 };
+// the larger of the two, NaN if either is: a plain `v > m ? v : m` drops a NaN step, and the measure built on the largest earlier step then
+// looked finite -- "a NaN measure never ends a sweep" held for G_A and g_b only
+__device__ __forceinline__ double max_or_nan(double v, double m) { return (v > m || v != v) ? v : m; }
 template <typename T>
 __device__ __forceinline__ int skip_decision(const double* Gs, const double* Gb, const double* Areg, const double* dmax /* [6]: max |delta| of the earlier iterations */,
                                              int dim, int cloud, const SkipArgs<T>& sk, bool live /* alive_k != 0 */, double ref /* mref[cloud] */) {
@@ -614,12 +617,12 @@ __global__ __launch_bounds__(WAVE) void step_bwd_kernel(const double* __restrict
         for (int j = 1 + tid; j <= sk.k; j += WAVE) {
             const T* dp = delta_k + (size_t)cloud * delta_stride - (size_t)j * 6;
 #pragma unroll
-            for (int i = 0; i < 6; ++i) { const double v = fabs((double)dp[i]); dm[i] = v > dm[i] ? v : dm[i]; }
+            for (int i = 0; i < 6; ++i) { const double v = fabs((double)dp[i]); dm[i] = max_or_nan(v, dm[i]); }
         }
 #pragma unroll
         for (int i = 0; i < 6; ++i) {
 #pragma unroll
-            for (int off = WAVE / 2; off > 0; off >>= 1) { const double o = __shfl_down(dm[i], off); dm[i] = o > dm[i] ? o : dm[i]; }
+            for (int off = WAVE / 2; off > 0; off >>= 1) { const double o = __shfl_down(dm[i], off); dm[i] = max_or_nan(o, dm[i]); }
         }
         if (tid == 0) {
 #pragma unroll
@@ -799,12 +802,12 @@ __global__ __launch_bounds__(BLOCK) void icp_small_backward_kernel(WeightParams 
             double dm[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
             for (int j = tid - WAVE; j < k; j += WAVE) {
 #pragma unroll
-                for (int i = 0; i < 6; ++i) { const double v = fabs((double)dlt[(size_t)j * 6 + i]); dm[i] = v > dm[i] ? v : dm[i]; }
+                for (int i = 0; i < 6; ++i) { const double v = fabs((double)dlt[(size_t)j * 6 + i]); dm[i] = max_or_nan(v, dm[i]); }
             }
 #pragma unroll
             for (int i = 0; i < 6; ++i) {
 #pragma unroll
-                for (int off = WAVE / 2; off > 0; off >>= 1) { const double o = __shfl_down(dm[i], off); dm[i] = o > dm[i] ? o : dm[i]; }
+                for (int off = WAVE / 2; off > 0; off >>= 1) { const double o = __shfl_down(dm[i], off); dm[i] = max_or_nan(o, dm[i]); }
             }
             if (tid == WAVE) {
 #pragma unroll
@@ -982,12 +985,12 @@ __global__ __launch_bounds__(BLOCK, sizeof(T) == 4 ? 2 : 1) void bwd_tail_kernel
             double dm[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
             for (int j = tid - WAVE; j < k; j += WAVE) {
 #pragma unroll
-                for (int i = 0; i < 6; ++i) { const double v = fabs((double)dlt[(size_t)j * 6 + i]); dm[i] = v > dm[i] ? v : dm[i]; }
+                for (int i = 0; i < 6; ++i) { const double v = fabs((double)dlt[(size_t)j * 6 + i]); dm[i] = max_or_nan(v, dm[i]); }
             }
 #pragma unroll
             for (int i = 0; i < 6; ++i) {
 #pragma unroll
-                for (int off = WAVE / 2; off > 0; off >>= 1) { const double o = __shfl_down(dm[i], off); dm[i] = o > dm[i] ? o : dm[i]; }
+                for (int off = WAVE / 2; off > 0; off >>= 1) { const double o = __shfl_down(dm[i], off); dm[i] = max_or_nan(o, dm[i]); }
             }
             if (tid == WAVE) {
 #pragma unroll
