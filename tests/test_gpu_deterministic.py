@@ -93,6 +93,58 @@ def test_float64_weights_against_default_and_oracle(icp_type):
         np.testing.assert_allclose(g.cpu().numpy(), r.numpy(), atol=1e-8 * max(1.0, float(r.abs().max())))
 
 
+def hub_pairs(N=2, n=1700, m=2000, big=300, small=12, seed=23):
+    """make_pairs' volumetric clouds (a 20 m cube) plus two isolated target rows 4 m outside the cube's faces, and two blobs of source points half a metre
+    from them: `big` points whose nearest target is the first rim row by a wide margin (the nearest point of the cube is 3 m further), `small` at the
+    second.  -> src (N, n + big + small, 3), tgt (N, m + 2, 6), the two rim rows' indices"""
+    src, tgt = make_pairs(N, n, m, seed=seed, dtype=torch.float64)
+    g = torch.Generator().manual_seed(seed)
+    rim = torch.tensor([[14.0, 0.5, -0.3, 0.0, 0.6, 0.8], [0.2, 14.0, 0.4, 0.6, 0.0, 0.8]], dtype=torch.float64)
+    blob = lambda k, ctr: torch.tensor(ctr, dtype=torch.float64) + 0.1 * torch.randn((N, k, 3), generator=g, dtype=torch.float64)
+    src = torch.cat((src, blob(big, [13.5, 0.5, -0.3]), blob(small, [0.2, 13.5, 0.4])), 1)
+    tgt = torch.cat((tgt, rim[None].repeat(N, 1, 1)), 1)
+    return src.contiguous(), tgt.contiguous(), (m, m + 1)
+
+
+@pytest.mark.parametrize("icp_type", ["pt2pl", "pt2pt"])
+def test_float64_hubs_against_default_and_oracle(icp_type):
+    """Long row lists in the deterministic form: a part of the source with no counterpart in the target, all of it matched to one rim row (DESIGN.md
+    section 8, item 5).  A list longer than DET_LIST_MAX = 24 is handed to far_apply_kernel, a shorter one is summed in slot order by its row's thread;
+    a contribution dropped the same way on every run passes the run-to-run test, so the gradients are held to the oracle's."""
+    K, big, small = 4, 300, 12
+    src, tgt, rims = hub_pairs(big=big, small=small)
+    N, n = src.shape[:2]
+    w = torch.rand(N, n, dtype=torch.float64, generator=torch.Generator().manual_seed(7)) * 0.5 + 0.5
+    kw = dict(trim_dist=5.0, loss_fn={"name": "huber", "metric": 1.0}, dim=3)
+    s_c, t_c = src.clone().requires_grad_(True), (tgt if icp_type == "pt2pl" else tgt[:, :, :3]).clone().requires_grad_(True)
+    T_c, w_c = torch.eye(4, dtype=torch.float64).repeat(N, 1, 1).requires_grad_(True), w.clone().requires_grad_(True)
+    rec = {}
+    ref = O.icp_batched(s_c, t_c, T_c, w_c if icp_type == "pt2pl" else w_c.repeat_interleave(3, dim=1), icp_type=icp_type, differentiable=True, max_iterations=K,
+                        tolerance=1e-12, const_iter=True, tanh_steepness=5.0, record=rec, **kw)
+    # the conditions, on the oracle's own matches and weights of the last iteration (before any GPU result is read)
+    idx = rec["idx"][-1]
+    w_last = ref["weights"].detach()[:, -1, :, 0]
+    w_last = w_last if icp_type == "pt2pl" else w_last[:, ::3]
+    DET_LIST_MAX = 24
+    for b in range(N):
+        deg = torch.bincount(idx[b], minlength=tgt.shape[1])
+        assert int(deg[rims[0]]) >= big > DET_LIST_MAX and 2 <= int(deg[rims[1]]) <= DET_LIST_MAX, (int(deg[rims[0]]), int(deg[rims[1]]))
+        for r in rims:
+            assert float(w_last[b][idx[b] == r].min()) > 0.1
+    (ref["T"][:, :3].sum() + 0.1 * ref["pc"].sum()).backward()
+    o1, g1 = run(src, tgt, K, True, icp_type=icp_type, weight=w, kw=kw)
+    o2, g2 = run(src, tgt, K, True, icp_type=icp_type, weight=w, kw=kw)
+    assert identical(g1, g2)
+    _, gd = run(src, tgt, K, False, icp_type=icp_type, weight=w, kw=kw)
+    close(g1, gd, 1e-10)
+    np.testing.assert_allclose(o1["T"].detach().cpu().numpy(), ref["T"].detach().numpy(), atol=1e-10)
+    for g, r in zip(g1, (s_c.grad, t_c.grad, T_c.grad, w_c.grad)):
+        assert torch.isfinite(g).all()
+        np.testing.assert_allclose(g.cpu().numpy(), r.numpy(), atol=1e-8 * max(1.0, float(r.abs().max())))
+    # the rim rows' own gradients are not small: a dropped list would show
+    assert float(t_c.grad[:, rims[0]].abs().max()) > 1e-3 * float(t_c.grad.abs().max())
+
+
 def test_tolerance_mode_bit_identical():
     src, tgt = make_pairs(8, 8192, 8192, seed=3, dtype=torch.float32)
     o1, g1 = run(src, tgt, 30, True, const_iter=False, tol=1e-4)
