@@ -1,4 +1,4 @@
-"""The cloud arguments of the point-cloud operators (normals, voxel, knn, fps, ball, group): one cloud, a padded batch with row counts, or a list.
+"""The cloud arguments of the point-cloud operators (normals, voxel, knn, fps, ball, group, match): one cloud, a padded batch with row counts, or a list.
 
 check / check_pair / check_slots validate on the host (no device is touched), place moves a checked batch to the compute device, restore
 cuts the library's (N, ...) results back to the caller's form and device.  What differs between the operators is an argument at their call
@@ -201,6 +201,26 @@ def pair(x, y, x_rows, y_rows, what):
     (form, bx, rx, lx), (_, by, ry, _) = check_pair(x, y, x_rows, y_rows, what)
     on_cpu, bx_d, rx_d = place(bx, rx, xyz=True)
     _, by_d, ry_d = place(by, ry, xyz=True)
+    return form, on_cpu, lx, bx.shape[1], by.shape[1], bx_d, by_d, rx_d, ry_d
+
+
+def pair_features(x, y, x_rows, y_rows, what, d_max):
+    """pair for two descriptor tables (match.py): every column takes part (1 <= D <= d_max, the same D on both sides) -> pair's tuple"""
+    cx = check(x, x_rows, what, "fx", "x_rows", empty_ok=True, min_cols=1)
+    cy = check(y, y_rows, what, "fy", "y_rows", empty_ok=True, min_cols=1)
+    (form, bx, rx, lx), (_, by, ry, _) = cx, cy
+    if cx[0] != cy[0]:
+        _err(what, "fx and fy must have the same form (single clouds, padded batches or lists), got %s and %s" % (cx[0], cy[0]))
+    if bx.dtype != by.dtype:
+        _err(what, "fx and fy must have one dtype, got %s and %s" % (bx.dtype, by.dtype))
+    if bx.device != by.device:
+        _err(what, "fx and fy must be on one device, got %s and %s" % (bx.device, by.device))
+    if bx.shape[0] != by.shape[0]:
+        _err(what, "fx and fy must hold the same number of clouds, got %d and %d" % (bx.shape[0], by.shape[0]))
+    if bx.shape[2] != by.shape[2] or bx.shape[2] > d_max:
+        _err(what, "fx and fy need the same number of channels D in [1, %d], got %d and %d" % (d_max, bx.shape[2], by.shape[2]))
+    on_cpu, bx_d, rx_d = place(bx, rx)
+    _, by_d, ry_d = place(by, ry)
     return form, on_cpu, lx, bx.shape[1], by.shape[1], bx_d, by_d, rx_d, ry_d
 
 

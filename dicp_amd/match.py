@@ -1,0 +1,249 @@
+"""Descriptor matching: exact nearest neighbours in feature space, the matching rules on top of them, and the closed-form rigid fit of the
+matched points -- where ICP's T_init comes from.
+
+    from dicp_amd.match import knn_features, match_features, align_correspondences
+    idx, d2 = match_features(fx, fy, mutual=True, ratio=0.8)        # the accepted row of fy for every row of fx, -1 where rejected
+    T0 = align_correspondences(x, y, idx)                           # (N, 4, 4): the weighted Procrustes fit of x_i -> y_idx(i)
+    out = ICP(icp_type="pt2pt").icp(x, y, T_init=T0)
+
+All on the GPU (libdicp_hip.so: dicp_knn_features / _backward / _backward_det, and the Kabsch kernels of the ICP loop), without the (n, m)
+distance matrix; nothing is read back from the device.
+"""
+import torch
+
+from . import _clouds, _lib
+from ._clouds import ROW, K_MIN, K_MAX, _check_deterministic
+from ._ops import _DT, _p
+from .group import _invert
+
+D_MAX = 256             # MATCH_D_MAX (csrc/dicp_match.h)
+FORMS = {None: _lib.MATCH_AUTO, "valu": _lib.MATCH_VALU, "mfma": _lib.MATCH_MFMA}
+
+
+class _KnnFeatures(torch.autograd.Function):
+    """(fx (N,n,D), fy (N,m,D)) -> (d2 (N,n,k), idx (N,n,k) int64): one library call per direction on the current stream."""
+
+    @staticmethod
+    def forward(ctx, x, y, rx, ry, k, form, det):
+        N, n, D = x.shape
+        m = y.shape[1]
+        dt, dev = _DT[x.dtype], x.device
+        need = _lib.load().dicp_knn_features_workspace_bytes(dt, N, m)
+        d2 = torch.empty((N, n, k), dtype=x.dtype, device=dev)
+        idx = torch.empty((N, n, k), dtype=torch.int64, device=dev)
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        _lib.call("dicp_knn_features", dev, dt, _p(x), _p(rx), n, _p(y), _p(ry), m, D, N, k, form, _p(d2), _p(idx), _p(ws), need)
+        ctx.save_for_backward(x, y, idx)
+        ctx.ry, ctx.det = ry, det
+        ctx.mark_non_differentiable(idx)
+        ctx.set_materialize_grads(False)
+        return d2, idx
+
+    @staticmethod
+    def backward(ctx, g_d2, _g_idx):
+        want_x, want_y = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if g_d2 is None or not (want_x or want_y):
+            return (None,) * 7
+        x, y, idx = ctx.saved_tensors
+        N, n, D = x.shape
+        m, k = y.shape[1], idx.shape[2]
+        dt, dev = _DT[x.dtype], x.device
+        g_d2 = g_d2.contiguous()
+        gx = torch.empty_like(x) if want_x else None
+        gy = torch.empty_like(y) if want_y else None
+        if ctx.det:                                         # the x-gradient from the same kernel (grad_y = NULL), the y-gradient stored once
+            if want_x:
+                _lib.call("dicp_knn_features_backward", dev, dt, _p(g_d2), _p(idx), _p(x), _p(y), n, m, D, N, k, _p(gx), None)
+            if want_y:
+                off, slots = _invert(idx, ctx.ry, m)
+                _lib.call("dicp_knn_features_backward_det", dev, dt, _p(g_d2), _p(idx), _p(ctx.ry), _p(x), _p(y), n, m, D, N, k, _p(off), _p(slots), _p(gy))
+        else:
+            if want_y:
+                _lib.call("dicp_zero", dev, _p(gy), gy.numel() * gy.element_size())
+            _lib.call("dicp_knn_features_backward", dev, dt, _p(g_d2), _p(idx), _p(x), _p(y), n, m, D, N, k, _p(gx), _p(gy))
+        return gx, gy, None, None, None, None, None
+
+
+def _check_form(form, fx, what):
+    """the private _form of knn_features -> the library's code; fx: the caller's argument, looked at for its dtype only"""
+    if form not in FORMS:
+        raise ValueError('%s: _form must be None, "valu" or "mfma", got %r' % (what, form))
+    first = fx[0] if isinstance(fx, (list, tuple)) and fx else fx
+    if form == "mfma" and isinstance(first, torch.Tensor) and first.dtype != torch.float32:
+        raise ValueError('%s: _form="mfma" needs float32, got %s' % (what, first.dtype))
+    return FORMS[form]
+
+
+def knn_features(fx, fy, k=1, x_rows=None, y_rows=None, deterministic=False, _form=None):
+    """The k nearest rows of fy for every row of fx in descriptor space, exactly, with gradients of the squared distances.
+
+    fx, fy: one table each (n, D) and (m, D); a padded batch each (N, n, D) and (N, m, D) with optional integer row counts x_rows / y_rows
+        (N,); or two lists of N tables.  Both in the same form, dtype (float32 or float64) and device, with the same D in [1, 256]; every
+        column takes part.  CPU tensors are computed on the GPU and returned on the CPU.
+    k: an int in [1, 32].  deterministic: a bool (anything else is a ValueError before any device work); see "Gradients".
+
+    Definition (hardware-independent; fma is the correctly rounded fused multiply-add of the inputs' dtype T, the channels c ascending):
+        h_j = T(0.5) q_j,  q = +0,  q = fma(y_jc, y_jc, q);        score(i, j): s = h_j,  s = fma(-x_ic, y_jc, s).
+    The candidates of query i of cloud b are the rows j < y_rows[b] whose score is finite: a row of either side with a non-finite channel has
+    no finite score, so it is nobody's neighbour and as a query gets none.  The result is the first k_eff = min(k, #candidates) candidates in
+    (score, index) order, and the slots stay in that order.  The returned d2 is recomputed for the winners only, r = +0, t = x_ic - y_jc,
+    r = fma(t, t, r): non-negative, exactly 0 for identical rows, free of the cancellation of |x|^2 + |y|^2 - 2 x.y.  Its order can differ from
+    the score's order at rounding level: d2 need not ascend over the slots in its last bits.  Slots beyond k_eff, and query rows at or past
+    x_rows[b], hold d2 = +inf and idx = -1, so the output feeds group_points / pool_neighbors / invert_neighbors unchanged.
+
+    Returns (d2, idx): (n, k) for single tables, (N, n, k) for a batch, lists of (n_b, k) for lists; d2 in fx's dtype, idx int64.
+
+    float32 runs on the matrix cores (v_mfma_f32_32x32x2_f32, whose result is the same fma chain), float64 on the vector unit; the private
+    _form ("valu" / "mfma") selects the float32 kernel for cross-checks: both give the same bits.
+
+    Gradients flow from d2 only.  The term of slot (i, s) naming row j is t_c = (T)(2 g_is (x_ic - y_jc)), formed in float64 and rounded once; an
+    entry with g == 0 or idx < 0 has none.  The gradient of fx[i, c] is the sum of the query's terms in slot order from +0, written once
+    (bit-reproducible); that of fy[j, c] the sum of -t_c, by default added with float atomics (the last bits can differ from run to run;
+    rows nobody names get 0).  With deterministic=True the forward and the fx-gradient are the default call's, bit for bit, and the
+    fy-gradient is summed per row over its list in the inverted index of the returned idx (group.invert_neighbors, built once inside the
+    backward and only when fy needs a gradient), in chunks of 64 list positions -- each from +0, the partials added in order, a single chunk as
+    it is; every element is stored once: no zero fill, no atomics.
+    """
+    _clouds._check_k(k, "knn_features", K_MIN, K_MAX)
+    _check_deterministic(deterministic, "knn_features")
+    code = _check_form(_form, fx, "knn_features")
+    form, on_cpu, lens, n, _, xb, yb, rx, ry = _clouds.pair_features(fx, fy, x_rows, y_rows, "knn_features", D_MAX)
+    d2, idx = _KnnFeatures.apply(xb, yb, rx, ry, k, code, deterministic)
+    return _clouds.restore(form, on_cpu, n, lens, [(ROW, d2), (ROW, idx)])
+
+
+def _check_rules(mutual, ratio, max_d2, what):
+    if not isinstance(mutual, bool):
+        raise ValueError("%s: mutual must be True or False, got %r" % (what, mutual))
+    if ratio is not None and (isinstance(ratio, bool) or not isinstance(ratio, (int, float)) or not (0.0 < float(ratio) <= 1.0)):
+        raise ValueError("%s: ratio must be None or a number in (0, 1], got %r" % (what, ratio))
+    if max_d2 is not None and (isinstance(max_d2, bool) or not isinstance(max_d2, (int, float)) or not (float(max_d2) >= 0.0)):
+        raise ValueError("%s: max_d2 must be None or a number >= 0, got %r" % (what, max_d2))
+
+
+def match_features(fx, fy, x_rows=None, y_rows=None, mutual=True, ratio=None, max_d2=None, deterministic=False):
+    """The accepted match in fy of every row of fx: nearest neighbour in descriptor space, mutual check, ratio test, distance gate.
+
+    fx, fy, x_rows, y_rows, deterministic: as knn_features.
+    ratio: None or a number in (0, 1] (Lowe's test on distances): the search takes k = 2, and a query is kept when d2_0 <= T(ratio ratio) d2_1;
+        a query with a single candidate (d2_1 = +inf) passes.
+    mutual: a bool; True runs the reverse k = 1 search (fy over fx, x_rows honoured) and keeps i when idx_yx[idx_xy[i]] == i.
+    max_d2: None or a number >= 0: a query is kept when d2_0 <= max_d2.
+
+    Returns (idx, d2): (n,) / (N, n) / lists of (n_b,); idx int64 -- the row of fy, -1 where the query is rejected or has no candidate --
+    and d2 in fx's dtype, +inf where rejected.  d2 carries knn_features' gradient for the accepted rows; the decisions carry none, and a
+    rejected row's gradient is exactly zero.  The rules read knn_features' outputs only; nothing is read back from the device.
+    """
+    _check_rules(mutual, ratio, max_d2, "match_features")
+    _check_deterministic(deterministic, "match_features")
+    form, on_cpu, lens, n, m, xb, yb, rx, ry = _clouds.pair_features(fx, fy, x_rows, y_rows, "match_features", D_MAX)
+    d2k, idxk = _KnnFeatures.apply(xb, yb, rx, ry, 1 if ratio is None else 2, _lib.MATCH_AUTO, deterministic)
+    d0, i0 = d2k[..., 0], idxk[..., 0]
+    with torch.no_grad():
+        keep = i0 >= 0
+        if ratio is not None:
+            r2 = torch.tensor(float(ratio) * float(ratio), dtype=d0.dtype, device=d0.device)
+            keep &= d0 <= r2 * d2k[..., 1]
+        if max_d2 is not None:
+            keep &= d0 <= max_d2
+        if mutual:
+            _, back = _KnnFeatures.apply(yb.detach(), xb.detach(), ry, rx, 1, _lib.MATCH_AUTO, False)
+            keep &= torch.gather(back[..., 0], 1, i0.clamp(min=0)) == torch.arange(xb.shape[1], device=i0.device)[None, :]
+    idx = torch.where(keep, i0, torch.full_like(i0, -1))
+    d2 = torch.where(keep, d0, torch.full_like(d0, float("inf")))
+    return _clouds.restore(form, on_cpu, n, lens, [(ROW, idx), (ROW, d2)])
+
+
+class _Align(torch.autograd.Function):
+    """(x (N,n,3), y (N,m,3), w (N,n)) with idx (N,n) int32 in [0, m) -> T (N,4,4): dicp_kabsch_accumulate under the identity pose, then
+    dicp_kabsch_step; the backward is dicp_kabsch_step_bwd, then dicp_kabsch_bwd into zeroed gradients."""
+
+    @staticmethod
+    def forward(ctx, x, y, w, idx, rows):
+        N, n, _ = x.shape
+        m = y.shape[1]
+        dt, dev = x.dtype, x.device
+        code = _DT[dt]
+        nblk = _lib.load().dicp_accumulate_blocks(n)
+        pose0 = torch.zeros((N, 12), dtype=dt, device=dev)
+        pose0[:, 0] = pose0[:, 4] = pose0[:, 8] = 1.0
+        partials = torch.empty((N, nblk, _lib.NACC_PAD), dtype=dt, device=dev)
+        pose = torch.empty((N, 12), dtype=dt, device=dev)
+        cost = torch.empty((N,), dtype=dt, device=dev)
+        save = torch.empty((N, _lib.KAB_SAVE), dtype=torch.float64, device=dev)
+        _lib.call("dicp_kabsch_accumulate", dev, code, _p(x), _p(y), 3, _p(idx), _p(pose0), _p(w), 0, 0.0, _p(rows), N, n, m, _p(partials))
+        _lib.call("dicp_kabsch_step", dev, code, _p(partials), nblk, _p(pose), _p(cost), _p(save), N)
+        T = torch.zeros((N, 4, 4), dtype=dt, device=dev)
+        T[:, :3, :3] = pose[:, :9].reshape(N, 3, 3)
+        T[:, :3, 3] = pose[:, 9:]
+        T[:, 3, 3] = 1.0
+        ctx.save_for_backward(x, y, w, idx, pose0, save)
+        ctx.rows = rows
+        return T
+
+    @staticmethod
+    def backward(ctx, gT):
+        x, y, w, idx, pose0, save = ctx.saved_tensors
+        N, n, _ = x.shape
+        m = y.shape[1]
+        dt, dev = x.dtype, x.device
+        code = _DT[dt]
+        gT = gT.contiguous()
+        gpose = torch.cat((gT[:, :3, :3].reshape(N, 9), gT[:, :3, 3]), dim=1).contiguous()
+        gacc = torch.empty((N, 16), dtype=dt, device=dev)
+        _lib.call("dicp_kabsch_step_bwd", dev, code, _p(gpose), _p(save), _p(gacc), N)
+        gx, gy, gw = torch.empty_like(x), torch.empty_like(y), torch.empty_like(w)
+        for t in (gx, gy, gw):                              # dicp_kabsch_bwd ADDS
+            _lib.call("dicp_zero", dev, _p(t), t.numel() * t.element_size())
+        _lib.call("dicp_kabsch_bwd", dev, code, _p(x), _p(y), 3, _p(idx), _p(pose0), _p(w), 0, 0.0, _p(gacc), _p(ctx.rows), N, n, m, _p(gx), _p(gy), _p(gw))
+        return gx, gy, gw, None, None
+
+
+def align_correspondences(x, y, idx, weight=None, x_rows=None):
+    """The rigid transform T (N, 4, 4) minimising sum_i w_i |C x_i + r - y_idx(i)|^2 over explicit correspondences, in closed form.
+
+    x (n, c) / (N, n, c), y (m, c) / (N, m, c): points, float32 or float64, columns 0:3 are used.  idx (n,) / (N, n) int64 or int32: the row of
+    y matched to every row of x, negative = no match (match_features' output as it is).  weight: None (1) or (n,) / (N, n) in the points'
+    dtype.  x_rows: optional (N,) row counts of a padded batch.  w_i = weight_i for i < x_rows[b] with idx_i >= 0, and 0 otherwise: the points
+    and the idx of such rows have no influence at all.  An idx >= m is a ValueError only when idx is a CPU tensor (no read-back from the
+    device: the kernel clamps it into [0, m - 1]).  A single pair of clouds returns (4, 4).
+
+    Gradients go to x, y (columns 0:3) and weight.
+
+    Limits, those of the ICP loop's SVD step whose kernels these are (dicp_kabsch_accumulate / _step / _step_bwd / _bwd):
+    the rotation is U diag(1, 1, det U det V) V^T, always proper; the sums are un-centred raw moments, so in float32 the accuracy far from the
+    origin is that of ICP's SVD step (centre the clouds first, or use float64).  A degenerate set of pairs -- no pair, all weights zero,
+    or fewer than three non-collinear pairs -- has no unique minimiser: the step kernel returns the proper rotation its SVD of the (rank-
+    deficient) covariance yields, with r fitting the weighted centroids, and for no pairs at all a non-finite pose (the weights' sum is 0);
+    the gradients at such a point are not meaningful.
+    """
+    what = "align_correspondences"
+    (form, bx, rx, _), (_, by, _, _) = _clouds.check_pair(x, y, x_rows, None, what)
+    if form == "list":
+        raise ValueError("%s: x and y must be single clouds or padded batches" % what)
+    if bx.shape[1] < 1 or by.shape[1] < 1:
+        raise ValueError("%s: x and y need at least one row" % what)
+    N, n, m = bx.shape[0], bx.shape[1], by.shape[1]
+    if not isinstance(idx, torch.Tensor) or idx.dtype not in (torch.int32, torch.int64):
+        raise ValueError("%s: idx must be an int32 or int64 tensor, got %s" % (what, getattr(idx, "dtype", type(idx).__name__)))
+    if tuple(idx.shape) != ((n,) if form == "single" else (N, n)) or idx.device != bx.device:
+        raise ValueError("%s: idx must hold one entry per row of x on x's device, shape %s, got %s on %s"
+                         % (what, (n,) if form == "single" else (N, n), tuple(idx.shape), idx.device))
+    if not idx.is_cuda and idx.numel() and int(idx.max()) >= m:
+        raise ValueError("%s: idx must be below y's %d rows" % (what, m))
+    if weight is not None:
+        if not isinstance(weight, torch.Tensor) or weight.dtype != bx.dtype or tuple(weight.shape) != tuple(idx.shape) or weight.device != bx.device:
+            raise ValueError("%s: weight must be a tensor of x's dtype and device with idx's shape" % what)
+    on_cpu, xd, rows = _clouds.place(bx, rx, xyz=False)
+    _, yd, _ = _clouds.place(by, None, xyz=False)
+    dev = xd.device
+    xd, yd = xd[..., :3].contiguous(), yd[..., :3].contiguous()
+    idx_d = idx.to(dev).reshape(N, n)
+    live = idx_d >= 0
+    w = torch.ones((N, n), dtype=xd.dtype, device=dev) if weight is None else weight.to(dev).reshape(N, n)
+    w = torch.where(live, w, torch.zeros((), dtype=xd.dtype, device=dev)).contiguous()
+    idx32 = torch.where(live, idx_d, torch.zeros_like(idx_d)).to(torch.int32).contiguous()
+    T = _Align.apply(xd, yd, w, idx32, rows)
+    if on_cpu:
+        T = T.cpu()
+    return T[0] if form == "single" else T

@@ -1096,6 +1096,35 @@ size_t dicp_outlier_workspace_bytes(int N, int m);
 int dicp_outlier_stats(int dtype, const void* d2, const int64_t* idx, const int32_t* rows, int N, int m, int k, double std_ratio,
                        double* mean_distance, double* stats, uint8_t* mask, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The exact k nearest rows in descriptor space (dicp_amd/match.py: knn_features / match_features; csrc/match.hip, the rules:
+ * csrc/dicp_match.h).  x (N,n,D) T, y (N,m,D) T, 1 <= D <= 256, 1 <= k <= 32 (DICP_ERR_SHAPE); x_rows / y_rows: optional (N) row counts as
+ * tgt_rows.  With fma the correctly rounded fused multiply-add of T and the channels c in ascending order:
+ *     h_j = T(0.5) q_j,  q = +0, q = fma(y_jc, y_jc, q);    score(i,j): s = h_j, s = fma(-x_ic, y_jc, s).
+ * The candidates of query i of cloud b are the rows j < y_rows[b] whose score is finite (a non-finite channel on either side leaves none);
+ * the result is the first k_eff = min(k, #candidates) of them in (score, index) order, in that order.  Written: idx (N,n,k) int64 and d2
+ * (N,n,k) T, d2 recomputed for the winners as r = +0, t = x_ic - y_jc, r = fma(t, t, r) (non-negative, 0 for identical rows; its order can
+ * differ from the score's at rounding level); slots past k_eff and query rows at or past x_rows[b] hold +inf / -1.  Pad rows are never
+ * candidates whatever they hold.  Nothing is read back; bit-reproducible and independent of the form.
+ *   form: DICP_MATCH_AUTO (float32: the matrix cores, float64: the vector unit), DICP_MATCH_VALU (one fma per channel per pair),
+ *   DICP_MATCH_MFMA (v_mfma_f32_32x32x2_f32, float32 only: DICP_ERR_ENUM with float64).  Both forms give the same bits.
+ *   workspace: dicp_knn_features_workspace_bytes(dtype, N, m) bytes (0 for bad arguments; the table h), 16-byte aligned.
+ * dicp_knn_features_backward: the gradient of d2.  The term of slot (i,s) naming row j is, per channel, t_c = (T)(2.0 (double)g_is
+ *   ((double)x_ic - (double)y_jc)), rounded once; a slot with g == 0 or idx outside [0, m) has none.  grad_x (N,n,D), optional: the sum of the
+ *   query's terms in slot order from +0, every element stored once (bit-reproducible).  grad_y (N,m,D), optional: -t_c is ADDED with float
+ *   atomics -- the caller zeroes it first (dicp_zero); rows nobody names keep 0.
+ * dicp_knn_features_backward_det: grad_y (N,m,D) from (offsets, slots) = dicp_invert_neighbors of idx with rows = y_rows and m: element
+ *   (j,c) is the sum of -t_c over the row's list in list order, in chunks of 64 list positions, each from +0, the partials added in order to a
+ *   total that starts at +0, a single chunk as it is (csrc/dicp_inverse.h); rows at or past y_rows[b] and rows nobody names get 0.  Every
+ *   element is stored exactly once: no zero fill, no atomics, bit-reproducible.  The kernel stays in range whatever offsets / slots hold. */
+enum { DICP_MATCH_AUTO = 0, DICP_MATCH_VALU = 1, DICP_MATCH_MFMA = 2 };
+size_t dicp_knn_features_workspace_bytes(int dtype, int N, int m);
+int dicp_knn_features(int dtype, const void* x, const int32_t* x_rows, int n, const void* y, const int32_t* y_rows, int m, int D, int N, int k,
+                      int form, void* d2, int64_t* idx, void* workspace, size_t workspace_bytes, void* stream);
+int dicp_knn_features_backward(int dtype, const void* g_d2, const int64_t* idx, const void* x, const void* y, int n, int m, int D, int N, int k,
+                               void* grad_x, void* grad_y, void* stream);
+int dicp_knn_features_backward_det(int dtype, const void* g_d2, const int64_t* idx, const int32_t* y_rows, const void* x, const void* y, int n, int m,
+                                   int D, int N, int k, const int32_t* offsets, const int32_t* slots, void* grad_y, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
