@@ -5,9 +5,10 @@ matched points -- where ICP's T_init comes from.
     idx, d2 = match_features(fx, fy, mutual=True, ratio=0.8)        # the accepted row of fy for every row of fx, -1 where rejected
     T0 = align_correspondences(x, y, idx)                           # (N, 4, 4): the weighted Procrustes fit of x_i -> y_idx(i)
     out = ICP(icp_type="pt2pt").icp(x, y, T_init=T0)
+    T0, inliers = ransac_correspondences(x, y, idx, threshold=0.05) # ... the same fit when many of the matches are wrong (RANSAC)
 
-All on the GPU (libdicp_hip.so: dicp_knn_features / _backward / _backward_det, and the Kabsch kernels of the ICP loop), without the (n, m)
-distance matrix; nothing is read back from the device.
+All on the GPU (libdicp_hip.so: dicp_knn_features / _backward / _backward_det, dicp_ransac_hypotheses / _score / _best,
+dicp_pair_residuals, and the Kabsch kernels of the ICP loop), without the (n, m) distance matrix; nothing is read back from the device.
 """
 import torch
 
@@ -217,7 +218,20 @@ def align_correspondences(x, y, idx, weight=None, x_rows=None):
     deficient) covariance yields, with r fitting the weighted centroids, and for no pairs at all a non-finite pose (the weights' sum is 0);
     the gradients at such a point are not meaningful.
     """
-    what = "align_correspondences"
+    form, on_cpu, xd, yd, idx_d, w, rows = _pair_arguments(x, y, idx, weight, x_rows, "align_correspondences")
+    T = _align(xd, yd, idx_d, w, rows)
+    if on_cpu:
+        T = T.cpu()
+    return T[0] if form == "single" else T
+
+
+_NO_T = object()
+
+
+def _pair_arguments(x, y, idx, weight, x_rows, what, T=_NO_T):
+    """The checks of align_correspondences (and of a transform T, where one is given; ValueError before any device work), then its
+    arguments on the device:
+    -> (form, on_cpu, x (N,n,3), y (N,m,3), idx (N,n) as given, weight (N,n) or None, rows (N,) int32 or None)."""
     (form, bx, rx, _), (_, by, _, _) = _clouds.check_pair(x, y, x_rows, None, what)
     if form == "list":
         raise ValueError("%s: x and y must be single clouds or padded batches" % what)
@@ -234,16 +248,188 @@ def align_correspondences(x, y, idx, weight=None, x_rows=None):
     if weight is not None:
         if not isinstance(weight, torch.Tensor) or weight.dtype != bx.dtype or tuple(weight.shape) != tuple(idx.shape) or weight.device != bx.device:
             raise ValueError("%s: weight must be a tensor of x's dtype and device with idx's shape" % what)
+    if T is not _NO_T:
+        shape = (4, 4) if form == "single" else (N, 4, 4)
+        if not isinstance(T, torch.Tensor) or T.dtype != bx.dtype or tuple(T.shape) != shape or T.device != bx.device:
+            raise ValueError("%s: T must be a %s tensor of x's dtype on x's device" % (what, shape))
     on_cpu, xd, rows = _clouds.place(bx, rx, xyz=False)
     _, yd, _ = _clouds.place(by, None, xyz=False)
     dev = xd.device
     xd, yd = xd[..., :3].contiguous(), yd[..., :3].contiguous()
     idx_d = idx.to(dev).reshape(N, n)
+    return form, on_cpu, xd, yd, idx_d, None if weight is None else weight.to(dev).reshape(N, n), rows
+
+
+def _align(xd, yd, idx_d, weight, rows):
+    """align_correspondences on _pair_arguments' tensors -> T (N, 4, 4)"""
+    N, n, dev = xd.shape[0], xd.shape[1], xd.device
     live = idx_d >= 0
-    w = torch.ones((N, n), dtype=xd.dtype, device=dev) if weight is None else weight.to(dev).reshape(N, n)
+    w = torch.ones((N, n), dtype=xd.dtype, device=dev) if weight is None else weight
     w = torch.where(live, w, torch.zeros((), dtype=xd.dtype, device=dev)).contiguous()
     idx32 = torch.where(live, idx_d, torch.zeros_like(idx_d)).to(torch.int32).contiguous()
-    T = _Align.apply(xd, yd, w, idx32, rows)
+    return _Align.apply(xd, yd, w, idx32, rows)
+
+
+H_MAX = 65536           # RANSAC_H_MAX (csrc/dicp_ransac.h)
+REFINE_MAX = 8
+
+
+def _pose12(T):
+    """(N, 4, 4) -> (N, 12): C row-major, then r"""
+    return torch.cat((T[:, :3, :3].reshape(-1, 9), T[:, :3, 3]), dim=1).contiguous()
+
+
+def _T44(pose):
+    """(N, 12) -> (N, 4, 4)"""
+    N = pose.shape[0]
+    T = torch.zeros((N, 4, 4), dtype=pose.dtype, device=pose.device)
+    T[:, :3, :3] = pose[:, :9].reshape(N, 3, 3)
+    T[:, :3, 3] = pose[:, 9:]
+    T[:, 3, 3] = 1.0
+    return T
+
+
+def _idx32(idx_d, m):
+    """idx as the kernels read it: int32, anything at or past m clamped to m (the kernels clamp into [0, m - 1])"""
+    return idx_d.clamp(min=-1, max=m).to(torch.int32).contiguous()
+
+
+def _residuals(xd, yd, idx32, rows, pose):
+    """dicp_pair_residuals on detached (N, n, 3) / (N, m, 3) points -> d2 (N, n)"""
+    N, n, _ = xd.shape
+    d2 = torch.empty((N, n), dtype=xd.dtype, device=xd.device)
+    _lib.call("dicp_pair_residuals", xd.device, _DT[xd.dtype], _p(xd), _p(yd), _p(idx32), _p(rows), _p(pose), N, n, yd.shape[1], _p(d2))
+    return d2
+
+
+def _ransac_stages(xd, yd, idx_d, weight, rows, threshold, hypotheses, seed, refine, _poses=None):
+    """Every stage of ransac_correspondences on _pair_arguments' tensors, as a dict: live (N, n) bool, pairs (N, n, 6), P (N,) int32,
+    index (N, n) int64, samples (N, H, 3) int32, poses (N, H, 12), counts (N, H) int32, best / best_count (N,) int32, pose_best (N, 12),
+    thr2 (0-d), sets [I_0 .. I_R] of (N, n) bool, accepted [(N,) bool per round], round_poses [(N, 12) per round: T_j's pose], inliers (N, n)
+    bool.  _poses (N, H, 12): the poses to
+    score instead of stage 1's (samples are then -1).  Nothing is read back."""
+    from .filter import _Select
+    N, n, _ = xd.shape
+    m, dt, dev = yd.shape[1], xd.dtype, xd.device
+    code = _DT[dt]
+    H = int(hypotheses)
+    with torch.no_grad():
+        x0, y0 = xd.detach(), yd.detach()
+        idx32 = _idx32(idx_d, m)
+        yg = torch.gather(y0, 1, idx32.clamp(min=0, max=m - 1).long()[..., None].expand(N, n, 3))
+        live = (idx32 >= 0) & torch.isfinite(x0).all(dim=-1) & torch.isfinite(yg).all(dim=-1)
+        if rows is not None:
+            live &= torch.arange(n, device=dev)[None, :] < rows[:, None]
+        pairs, P, index = _Select.apply(torch.cat((x0, yg), dim=-1).contiguous(), live.contiguous(), None, True)
+        if _poses is None:
+            poses = torch.empty((N, H, 12), dtype=dt, device=dev)
+            samples = torch.empty((N, H, 3), dtype=torch.int32, device=dev)
+            _lib.call("dicp_ransac_hypotheses", dev, code, _p(pairs), _p(P), N, n, H, int(seed) & 0xFFFFFFFF, _p(poses), _p(samples))
+        else:
+            poses = _poses.to(device=dev, dtype=dt).reshape(N, H, 12).contiguous()
+            samples = torch.full((N, H, 3), -1, dtype=torch.int32, device=dev)
+        counts = torch.empty((N, H), dtype=torch.int32, device=dev)
+        _lib.call("dicp_zero", dev, _p(counts), counts.numel() * 4)
+        _lib.call("dicp_ransac_score", dev, code, _p(pairs), _p(P), _p(poses), N, n, H, float(threshold), _p(counts))
+        best = torch.empty((N,), dtype=torch.int32, device=dev)
+        best_count = torch.empty((N,), dtype=torch.int32, device=dev)
+        pose_best = torch.empty((N, 12), dtype=dt, device=dev)
+        _lib.call("dicp_ransac_best", dev, code, _p(counts), _p(poses), _p(P), N, H, _p(best), _p(best_count), _p(pose_best))
+        thr2 = torch.full((), float(threshold) * float(threshold), dtype=dt, device=dev)        # (the product in double, rounded once to T)
+        some = (P >= 3)[:, None]
+        inl = (_residuals(x0, y0, idx32, rows, pose_best) <= thr2) & some
+        sets, accepted, round_poses = [inl], [], []
+        minus = torch.full_like(idx_d, -1)
+        for _ in range(int(refine)):
+            pj = _pose12(_align(x0, y0, torch.where(inl, idx_d, minus), weight if weight is None else weight.detach(), rows))
+            round_poses.append(pj)
+            new = (_residuals(x0, y0, idx32, rows, pj) <= thr2) & some
+            ok = new.sum(dim=1) >= inl.sum(dim=1)
+            inl = torch.where(ok[:, None], new, inl)
+            sets.append(inl)
+            accepted.append(ok)
+    return dict(live=live, pairs=pairs, P=P, index=index, samples=samples, poses=poses, counts=counts, best=best, best_count=best_count,
+                pose_best=pose_best, thr2=thr2, sets=sets, accepted=accepted, round_poses=round_poses, inliers=inl)
+
+
+def _check_ransac(threshold, hypotheses, seed, refine, return_hypothesis, what):
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float)) or not (0.0 < float(threshold) < float("inf")):
+        raise ValueError("%s: threshold must be a finite number > 0, got %r" % (what, threshold))
+    if isinstance(hypotheses, bool) or not isinstance(hypotheses, int) or not (1 <= hypotheses <= H_MAX):
+        raise ValueError("%s: hypotheses must be an int in [1, %d], got %r" % (what, H_MAX, hypotheses))
+    if seed is not None and (isinstance(seed, bool) or not isinstance(seed, int)):
+        raise ValueError("%s: seed must be None or an int, got %r" % (what, seed))
+    if isinstance(refine, bool) or not isinstance(refine, int) or not (0 <= refine <= REFINE_MAX):
+        raise ValueError("%s: refine must be an int in [0, %d], got %r" % (what, REFINE_MAX, refine))
+    if not isinstance(return_hypothesis, bool):
+        raise ValueError("%s: return_hypothesis must be True or False, got %r" % (what, return_hypothesis))
+
+
+def ransac_correspondences(x, y, idx, threshold, hypotheses=1024, seed=None, refine=1, weight=None, x_rows=None, return_hypothesis=False):
+    """A rigid transform from putative correspondences of which many are wrong: RANSAC over minimal samples of three pairs, then
+    LO-RANSAC refits on the inliers -- all on the GPU, per cloud, with no read-back.
+
+    x, y, idx, weight, x_rows: exactly as align_correspondences (single clouds or padded batches, float32 or float64, columns 0:3, idx
+        int32 or int64 with negative = no match; CPU tensors are computed on the GPU and returned on the CPU).
+    threshold: a finite number > 0, the inlier distance (not squared).  hypotheses: an int H in [1, 65536].  refine: an int R in [0, 8].
+    seed: None or an int (its low 32 bits count); None draws one 32-bit seed on the host from torch's CPU generator.
+    Anything else is a ValueError before any device work.
+
+    Definition (hardware-independent; T the points' dtype, fma its correctly rounded fused multiply-add):
+     1. Row i of cloud b is live when i < x_rows[b], idx_i >= 0, and x_i[0:3] and y_j[0:3] are finite with j = min(idx_i, m - 1).  The live
+        list is the live rows in ascending i, P_b of them.
+     2. The sample of hypothesis h, in 32-bit wrap-around integers (mix32: the hash of the Gumbel noise):
+            kc = mix32(seed ^ cloud 0x9E3779B9), kh = mix32(kc ^ h 0x85EBCA6B), u_t = mix32(kh ^ (t 0xC2B2AE35 + 0x27D4EB2F)), t = 0, 1, 2;
+            mulhi(u, q) = (u q) >> 32;  a = mulhi(u0, P);  b = mulhi(u1, P - 1), b += (b >= a);
+            c = mulhi(u2, P - 2), c += (c >= min(a, b)), c += (c >= max(a, b)):  three distinct positions of the live list.
+        A cloud with P < 3 has no hypotheses: best -1, best_count 0, no inliers, T_best the identity, T = align_correspondences' for no pairs.
+     3. The minimal fit in double: the 18 Kabsch sums from 0, the pairs a, b, c added in that order at weight 1, then the closed form of
+        align_correspondences (proper rotation, rank-deficient completion); C (row-major) and r are rounded once to T.
+     4. The residual of a pair under a pose in T: q_a = fma(C_a2, x_2, fma(C_a1, x_1, fma(C_a0, x_0, r_a))), e_a = q_a - y_a, d = +0, then
+        d = fma(e_a, e_a, d) for a = 0, 1, 2.  The pair is an inlier iff d <= thr2 = T((double)threshold (double)threshold); a NaN d never is.
+     5. count_h = the live pairs that are inliers of pose h; best = the h with the largest count, ties to the lowest h; T_best its pose.
+     6. I_0 = the inliers of T_best.  For j = 1 .. R: T_j = align_correspondences on the pairs of I_{j-1} (with weight, no gradient), I_j the
+        inliers of T_j's pose in T; a cloud accepts round j iff |I_j| >= |I_{j-1}|, otherwise it keeps I_{j-1}.
+        inliers = I_R and T = align_correspondences(x, y, where(inliers, idx, -1), weight, x_rows).
+
+    Returns (T, inliers): T (N, 4, 4) or (4, 4) for a single pair of clouds, inliers (N, n) or (n,) torch.bool in the original row order;
+    with return_hypothesis=True also best (N,) int32, best_count (N,) int32 and T_best (N, 4, 4), the winning minimal-sample pose.
+
+    Gradients flow through the final fit only, to x, y and weight (align_correspondences' backward on the final inlier set); the
+    decisions carry none.  Nothing is read back and no launch depends on device data: with an int seed on device tensors the call can sit
+    in a captured graph.  Integer counts, no float atomics: the result is bit-reproducible.
+
+    Kernels (libdicp_hip.so): dicp_select_rows packs the live pairs, dicp_ransac_hypotheses / _score / _best, dicp_pair_residuals.
+    """
+    what = "ransac_correspondences"
+    _check_ransac(threshold, hypotheses, seed, refine, return_hypothesis, what)
+    form, on_cpu, xd, yd, idx_d, w, rows = _pair_arguments(x, y, idx, weight, x_rows, what)
+    if seed is None:
+        seed = int(torch.randint(0, 1 << 32, (1,), dtype=torch.int64).item())       # (a CPU tensor: no device read-back)
+    st = _ransac_stages(xd, yd, idx_d, w, rows, threshold, hypotheses, seed, refine)
+    inl = st["inliers"]
+    T = _align(xd, yd, torch.where(inl, idx_d, torch.full_like(idx_d, -1)), w, rows)
+    outs = [T, inl]
+    if return_hypothesis:
+        outs += [st["best"], st["best_count"], _T44(st["pose_best"])]
     if on_cpu:
-        T = T.cpu()
-    return T[0] if form == "single" else T
+        outs = [t.cpu() for t in outs]
+    if form == "single":
+        outs[0], outs[1] = outs[0][0], outs[1][0]
+    return tuple(outs)
+
+
+def correspondence_residuals(x, y, idx, T, x_rows=None):
+    """The squared residual of every correspondence under a rigid transform, by rule 4 of ransac_correspondences.
+
+    x, y, idx, x_rows: as align_correspondences.  T: (N, 4, 4), or (4, 4) for a single pair of clouds, in the points' dtype on their device;
+    its rows 0:3 are the pose.  Returns d2 (N, n) / (n,) in x's dtype: d for a live row, +inf for one that is not.  No gradient.
+    """
+    what = "correspondence_residuals"
+    form, on_cpu, xd, yd, idx_d, _, rows = _pair_arguments(x, y, idx, None, x_rows, what, T)
+    N = xd.shape[0]
+    with torch.no_grad():
+        d2 = _residuals(xd.detach(), yd.detach(), _idx32(idx_d, yd.shape[1]), rows, _pose12(T.detach().to(xd.device).reshape(N, 4, 4)))
+    if on_cpu:
+        d2 = d2.cpu()
+    return d2[0] if form == "single" else d2

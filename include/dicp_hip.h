@@ -1125,6 +1125,34 @@ int dicp_knn_features_backward(int dtype, const void* g_d2, const int64_t* idx, 
 int dicp_knn_features_backward_det(int dtype, const void* g_d2, const int64_t* idx, const int32_t* y_rows, const void* x, const void* y, int n, int m,
                                    int D, int N, int k, const int32_t* offsets, const int32_t* slots, void* grad_y, void* stream);
 
+/* RANSAC over explicit correspondences (dicp_amd/match.py: ransac_correspondences / correspondence_residuals; csrc/ransac.hip, the rules:
+ * csrc/dicp_ransac.h).  pairs (N,n,6) T: every cloud's live pairs (x[0:3], y[0:3]) packed first, in ascending row order, as dicp_select_rows
+ * leaves them; P (N) int32: their number, clamped into [0, n].  1 <= H <= 65536 hypotheses (DICP_ERR_SHAPE).  fma is the correctly rounded
+ * fused multiply-add of T.  Nothing is read back; no float atomics: every output is bit-reproducible.
+ * dicp_ransac_hypotheses: samples (N,H,3) int32 and poses (N,H,12) T (C row-major, then r).  In 32-bit wrap-around integers, mix32 the hash of
+ *   the Gumbel noise: kc = mix32(seed ^ cloud 0x9E3779B9), kh = mix32(kc ^ h 0x85EBCA6B), u_t = mix32(kh ^ (t 0xC2B2AE35 + 0x27D4EB2F)); with
+ *   mulhi(u, q) = (u q) >> 32:  a = mulhi(u0, P); b = mulhi(u1, P - 1), b += (b >= a); c = mulhi(u2, P - 2), c += (c >= min(a, b)),
+ *   c += (c >= max(a, b)).  The 18 Kabsch sums start at 0 in double, the packed rows a, b, c are added in that order at weight 1, and the
+ *   pose is that of dicp_kabsch_step's closed form (proper rotation, rank-deficient completion), each value rounded once to T.  A cloud with
+ *   P < 3 gets samples -1 and identity poses.
+ * dicp_ransac_score: counts (N,H) int32 += the number of packed pairs j < P with d <= thr2 under pose h, thr2 = T(threshold threshold) (the
+ *   product in double; threshold finite and > 0: DICP_ERR_SHAPE), d = +0, then d = fma(e_a, e_a, d) for a = 0, 1, 2 with e_a = q_a - y_a,
+ *   q_a = fma(C_a2, x_2, fma(C_a1, x_1, fma(C_a0, x_0, r_a))); a NaN d never counts.  Integer atomics: the caller zeroes counts first
+ *   (dicp_zero).  A cloud with P < 3 adds nothing.  A workgroup takes 256 hypotheses x dicp_ransac_slice() pairs.
+ * dicp_ransac_best: best (N) int32 = the h with the largest count, ties to the lowest h; best_count (N) int32; pose_best (N,12) T = its pose.
+ *   P < 3: -1, 0, the identity.
+ * dicp_pair_residuals: d2 (N,n) T = d of row i under the cloud's one pose (N,12) T for a live row -- i < x_rows[b], idx >= 0, x_i[0:3] and
+ *   y_j[0:3] finite with j = min(idx, m - 1) -- and +inf otherwise.  x (N,n,3) T, y (N,m,3) T, idx (N,n) int32; x_rows optional. */
+int dicp_ransac_slice(void);
+int dicp_ransac_hypotheses(int dtype, const void* pairs, const int32_t* P, int N, int n, int H, uint32_t seed, void* poses, int32_t* samples,
+                           void* stream);
+int dicp_ransac_score(int dtype, const void* pairs, const int32_t* P, const void* poses, int N, int n, int H, double threshold, int32_t* counts,
+                      void* stream);
+int dicp_ransac_best(int dtype, const int32_t* counts, const void* poses, const int32_t* P, int N, int H, int32_t* best, int32_t* best_count,
+                     void* pose_best, void* stream);
+int dicp_pair_residuals(int dtype, const void* x, const void* y, const int32_t* idx, const int32_t* x_rows, const void* pose, int N, int n, int m,
+                        void* d2, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
