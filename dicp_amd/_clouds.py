@@ -1,6 +1,6 @@
-"""The cloud arguments of the point-cloud operators (normals, voxel, knn, fps, ball, group, match): one cloud, a padded batch with row counts, or a list.
+"""The cloud arguments of the point-cloud operators (normals, voxel, knn, fps, ball, group, match, fpfh): one cloud, a padded batch with row counts, or a list.
 
-check / check_pair / check_slots validate on the host (no device is touched), place moves a checked batch to the compute device, restore
+check / check_pair / check_slots / check_table validate on the host (no device is touched), place moves a checked batch to the compute device, restore
 cuts the library's (N, ...) results back to the caller's form and device.  What differs between the operators is an argument at their call
 site.
 """
@@ -176,6 +176,41 @@ def check_mask(t, what, name, like):
     batch = t.unsqueeze(0) if t.dim() == 1 else t
     if tuple(batch.shape) != tuple(other.shape[:2]):
         _err(what, "%s must hold one entry per row, shape %s, got %s" % (name, tuple(other.shape[1:2] if form == "single" else other.shape[:2]), tuple(t.shape)))
+    return batch
+
+
+def check_table(t, what, name, like, cols):
+    """A table with one row of exactly `cols` values per point -- normals -- in the form of the points it goes with: (m, cols), (N, m, cols)
+    or a list of (m_b, cols) -> batch (N, m, cols) (a list is padded with 0); ValueError for anything invalid.
+
+    like: the checked form, batch and list lengths (form, batch, lens) of the points: the same form, dtype, device, cloud and row counts."""
+    form, other, lens = like
+    is_list = isinstance(t, (list, tuple))
+    items = list(t) if is_list else [t]
+    if is_list and not items:
+        _err(what, "%s is an empty list" % name)
+    for i, c in enumerate(items):
+        nm = "%s[%d]" % (name, i) if is_list else name
+        if not isinstance(c, torch.Tensor):
+            _err(what, "%s must be a tensor, got %s" % (nm, type(c).__name__))
+        if c.dtype != other.dtype:
+            _err(what, "%s must have the dtype of the points, %s, got %s" % (nm, other.dtype, c.dtype))
+        if c.device != other.device:
+            _err(what, "%s and the points must be on one device, got %s and %s" % (nm, c.device, other.device))
+        if (is_list and c.dim() != 2) or c.dim() < 1 or c.shape[-1] != cols:
+            _err(what, "%s must have %d columns per row, got shape %s" % (nm, cols, tuple(c.shape)))
+    if not is_list and t.dim() not in (2, 3):
+        _err(what, "%s must be (m, %d), (N, m, %d) or a list of (m_b, %d), got shape %s" % (name, cols, cols, cols, tuple(t.shape)))
+    mine = "list" if is_list else ("single" if t.dim() == 2 else "batch")
+    if mine != form:
+        _err(what, "%s must have the form of the points (single clouds, padded batches or lists), got %s and %s" % (name, mine, form))
+    if is_list:
+        if [c.shape[0] for c in items] != list(lens):
+            _err(what, "%s must hold one row per point of every cloud, got lengths %s for clouds of %s rows" % (name, [c.shape[0] for c in items], list(lens)))
+        return torch.nn.utils.rnn.pad_sequence(items, batch_first=True)
+    batch = t.unsqueeze(0) if t.dim() == 2 else t
+    if tuple(batch.shape[:2]) != tuple(other.shape[:2]):
+        _err(what, "%s must hold one row per point, shape %s, got %s" % (name, tuple(other.shape[1:2] if form == "single" else other.shape[:2]) + (cols,), tuple(t.shape)))
     return batch
 
 

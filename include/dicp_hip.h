@@ -1153,6 +1153,28 @@ int dicp_ransac_best(int dtype, const int32_t* counts, const void* poses, const 
 int dicp_pair_residuals(int dtype, const void* x, const void* y, const int32_t* idx, const int32_t* x_rows, const void* pose, int N, int n, int m,
                         void* d2, void* stream);
 
+/* FPFH descriptors, 33 channels (dicp_amd/fpfh.py: fpfh_features / compute_fpfh; csrc/fpfh.hip, the rules: csrc/dicp_fpfh.h).  points
+ * (N,m,c) T with c >= 3 (columns 0:3 are read), normals (N,m,3) T, idx (N,m,k) int64 (idx64 = 1) or int32 (idx64 = 0; anything else:
+ * DICP_ERR_ENUM), a search of every cloud against ITSELF with 1 <= k <= 32; rows: optional (N) row counts.  radius: 0 for none, otherwise
+ * finite and > 0 (DICP_ERR_SHAPE); radius2 = radius radius in double.  Everything is computed in double from the exactly converted
+ * inputs with + - * / sqrt only, no fma; nothing is read back; no float atomics: every output is bit-reproducible.
+ *   Row i is OK when its coordinates and normal components are finite and the normal is not zero.  Slot (i,s) naming j = idx[b,i,s] is NEAR
+ *   when i < rows[b], 0 <= j < rows[b] (so nothing is read out of range whatever idx holds), j != i, both rows are OK, r2 = (dx dx + dy dy)
+ *   + dz dz > 0 for d = p_j - p_i, and r2 <= radius2 if there is a radius.  A near slot is a PAIR when its Darboux frame exists (v.v > 0).
+ * dicp_fpfh_spfh: the bin counts of the pairs of every row -- theta in [0,11), alpha in [11,22), phi in [22,33), the features, their order
+ *   of operations and the bin rules as csrc/dicp_fpfh.h states them -- into the internal table in `workspace` (48 bytes per row: the 33
+ *   counts, the number of pairs c_i, the OK flag) and, if spfh is not NULL, into spfh (N,m,33) bytes.  Rows at or past rows[b] get zeros.
+ * dicp_fpfh_combine: out (N,m,33) T from the table that dicp_fpfh_spfh left for the SAME points, idx, rows and radius: with s_j[ch] =
+ *   (100 cnt[j,ch]) / c_j (0 for c_j = 0), over the near slots of row i in slot order from +0, acc[ch] = acc[ch] + (1 / r2) s_j[ch] (the
+ *   product rounded first); S = the sum of acc over a feature's 11 channels in ascending order from +0; out[ch] = (S != 0 ? acc[ch]
+ *   (100 / S) : 0) + s_i[ch], rounded once to T.  Rows that are not OK or at or past rows[b] get 33 zeros.
+ *   workspace: dicp_fpfh_workspace_bytes(N, m) bytes (0 for bad arguments), 256-byte aligned. */
+size_t dicp_fpfh_workspace_bytes(int N, int m);
+int dicp_fpfh_spfh(int dtype, const void* points, int c, const void* normals, const void* idx, int idx64, const int32_t* rows, int N, int m, int k,
+                   double radius, void* workspace, size_t workspace_bytes, uint8_t* spfh, void* stream);
+int dicp_fpfh_combine(int dtype, const void* points, int c, const void* idx, int idx64, const int32_t* rows, int N, int m, int k, double radius,
+                      const void* workspace, size_t workspace_bytes, void* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
