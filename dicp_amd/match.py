@@ -7,8 +7,15 @@ matched points -- where ICP's T_init comes from.
     out = ICP(icp_type="pt2pt").icp(x, y, T_init=T0)
     T0, inliers = ransac_correspondences(x, y, idx, threshold=0.05) # ... the same fit when many of the matches are wrong (RANSAC)
 
-All on the GPU (libdicp_hip.so: dicp_knn_features / _backward / _backward_det, dicp_ransac_hypotheses / _score / _best,
-dicp_pair_residuals, and the Kabsch kernels of the ICP loop), without the (n, m) distance matrix; nothing is read back from the device.
+The hard decisions above carry no gradient.  The soft form does: every row of fx gets the softmax-weighted mean of the target's points,
+and the same closed-form fit then makes the pose differentiable in both descriptor tables:
+
+    soft, idx, prob = soft_match_features(fx, fy, y, temperature=0.1, return_best=True)
+    T0 = align_correspondences(x, soft, torch.arange(n).expand(N, n), weight=prob)
+
+All on the GPU (libdicp_hip.so: dicp_knn_features / _backward / _backward_det, dicp_soft_match / _backward, dicp_ransac_hypotheses /
+_score / _best, dicp_pair_residuals, and the Kabsch kernels of the ICP loop), without the (n, m) distance matrix; nothing is read back
+from the device.
 """
 import torch
 
@@ -18,6 +25,7 @@ from ._ops import _DT, _p
 from .group import _invert
 
 D_MAX = 256             # MATCH_D_MAX (csrc/dicp_match.h)
+BWD_MFMA_D = 128        # SOFT_BWD_MFMA_D (csrc/softmatch.hip): the widest table the matrix-core backward of soft_match_features takes
 FORMS = {None: _lib.MATCH_AUTO, "valu": _lib.MATCH_VALU, "mfma": _lib.MATCH_MFMA}
 
 
@@ -111,6 +119,123 @@ def knn_features(fx, fy, k=1, x_rows=None, y_rows=None, deterministic=False, _fo
     form, on_cpu, lens, n, _, xb, yb, rx, ry = _clouds.pair_features(fx, fy, x_rows, y_rows, "knn_features", D_MAX)
     d2, idx = _KnnFeatures.apply(xb, yb, rx, ry, k, code, deterministic)
     return _clouds.restore(form, on_cpu, n, lens, [(ROW, d2), (ROW, idx)])
+
+
+C_MAX = 8               # SOFT_C_MAX (csrc/dicp_softmatch.h)
+
+
+class _SoftMatch(torch.autograd.Function):
+    """(fx (N,n,D), fy (N,m,D), values (N,m,C)) -> (out (N,n,C), idx (N,n) int64, prob (N,n)): one library call per direction on the
+    current stream; lse (N,n) is kept for the backward."""
+
+    @staticmethod
+    def forward(ctx, x, y, v, rx, ry, tau, form):
+        N, n, D = x.shape
+        m, C = y.shape[1], v.shape[2]
+        dt, dev = _DT[x.dtype], x.device
+        need = _lib.load().dicp_soft_match_workspace_bytes(dt, N, m)
+        out = torch.empty((N, n, C), dtype=x.dtype, device=dev)
+        lse = torch.empty((N, n), dtype=x.dtype, device=dev)
+        idx = torch.empty((N, n), dtype=torch.int64, device=dev)
+        prob = torch.empty((N, n), dtype=x.dtype, device=dev)
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        _lib.call("dicp_soft_match", dev, dt, _p(x), _p(rx), n, _p(y), _p(ry), m, D, N, _p(v), C, tau, form, _p(out), _p(lse), _p(idx), _p(prob), _p(ws), need)
+        ctx.save_for_backward(x, y, v, out, lse)
+        ctx.rx, ctx.ry, ctx.tau, ctx.form = rx, ry, tau, form
+        ctx.mark_non_differentiable(idx, prob)
+        ctx.set_materialize_grads(False)
+        return out, idx, prob
+
+    @staticmethod
+    def backward(ctx, g, _g_idx, _g_prob):
+        want = ctx.needs_input_grad[:3]
+        if g is None or not any(want):
+            return (None,) * 7
+        x, y, v, out, lse = ctx.saved_tensors
+        N, n, D = x.shape
+        m, C = y.shape[1], v.shape[2]
+        dt, dev = _DT[x.dtype], x.device
+        g = g.contiguous()
+        gx, gy, gv = (torch.empty_like(t) if w else None for t, w in zip((x, y, v), want))      # every element is stored by the kernels
+        need = _lib.load().dicp_soft_match_workspace_bytes(dt, N, m)
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        form = _lib.MATCH_AUTO if ctx.form == _lib.MATCH_MFMA and D > BWD_MFMA_D else ctx.form        # (wider tables: the vector unit)
+        _lib.call("dicp_soft_match_backward", dev, dt, _p(x), _p(ctx.rx), n, _p(y), _p(ctx.ry), m, D, N, _p(v), C, ctx.tau, form, _p(out), _p(lse), _p(g),
+                  _p(gx), _p(gy), _p(gv), _p(ws), need)
+        return gx, gy, gv, None, None, None, None
+
+
+def _check_temperature(temperature, fx, what):
+    """a Python number > 0 whose scale -2 / temperature is a finite non-zero number of the tables' dtype -> float"""
+    if isinstance(temperature, bool) or not isinstance(temperature, (int, float)) or not (0.0 < float(temperature) < float("inf")):
+        raise ValueError("%s: temperature must be a finite Python number > 0, got %r" % (what, temperature))
+    first = fx[0] if isinstance(fx, (list, tuple)) and fx else fx
+    if isinstance(first, torch.Tensor) and first.dtype in _DT:
+        c = torch.tensor(-2.0 / float(temperature), dtype=torch.float64).to(first.dtype)
+        if not bool(torch.isfinite(c)) or float(c) == 0.0:
+            raise ValueError("%s: -2 / temperature must be a finite non-zero %s, got temperature %r" % (what, first.dtype, temperature))
+    return float(temperature)
+
+
+def soft_match_features(fx, fy, values, temperature, x_rows=None, y_rows=None, return_best=False, _form=None):
+    """Soft matches of two descriptor tables: for every row of fx the softmax-weighted mean of `values`, differentiable in fx, fy and values.
+
+    fx, fy, x_rows, y_rows: as knn_features (a single table each, padded batches with optional row counts, or lists; float32 or float64;
+        the same D in [1, 256]; CPU tensors are computed on the GPU and returned on the CPU).
+    values: one row of C columns per row of fy, 1 <= C <= 8, in fy's form, dtype and device -- the target's xyz, or xyz + normal.
+    temperature: a finite Python number tau > 0 (anything else is a ValueError before any device work).  A learnable temperature needs no
+        gradient here: scaling both tables by tau^(-1/2) is the same operator at temperature 1.
+    return_best: a bool; True also returns the hard winner and its probability.
+
+    Definition (hardware-independent for every decision; T the dtype, fma and the channel order knn_features'):
+        the score s_ij and the candidates of query i are knn_features', bit for bit (rows j < y_rows[b] with a finite score);
+        c = (T)(-2.0 / tau), rounded once;  l_ij = c s_ij (one rounding);  p_ij = exp(l_ij - lse_i) over the candidates;
+        out_i = sum_j p_ij values_j;  idx_i = the first candidate in (score, index) order = knn_features(k=1)'s, ties included;
+        prob_i = p at idx_i.
+    s_ij = (|x_i - y_j|^2 - |x_i|^2) / 2, so p is softmax_j(-|fx_i - fy_j|^2 / tau) exactly in exact arithmetic: the per-query constant
+    cancels.  A query at or past x_rows[b], or without a candidate, gets a zero row, idx -1, prob 0 and exactly zero gradients whatever
+    cotangent arrives; a row of fy at or past y_rows[b] enters no softmax and gets zero gradient whatever it and its values hold.  values
+    are never examined: a non-finite value in a row below the count leaves that cloud's outputs unspecified (and nothing out of range).
+
+    Returns out (n, C) / (N, n, C) / a list of (n_b, C); with return_best=True (out, idx, prob), idx int64 and prob in fx's dtype with
+    one entry per row of fx.  idx and prob carry no gradient.
+
+    The sums are an online softmax with a running maximum (|x|^2 / tau alone would overflow exp at small tau), in float32 with the scores
+    on the matrix cores (v_mfma_f32_32x32x2_f32), in float64 on the vector unit; the (n, m) matrix is never formed.  The private _form
+    ("valu" / "mfma") selects the float32 kernel for cross-checks: the two agree on idx exactly and on out to rounding (their orders of
+    summation differ).
+
+    float32 limit: the logits inherit the score's cancellation, an absolute error of about D u (|x||y| + |y|^2 / 2) 2 / tau with
+    u = 2^-24.  For small tau normalise or centre the descriptors, or use float64.
+
+    Gradients of out's cotangent g, with delta_i = g_i . out_i and a_ij = p_ij (g_i . values_j - delta_i):
+        gfx_i = -c sum_j a_ij fy_j,   gfy_j = c (fy_j sum_i a_ij - sum_i a_ij fx_i),   gvalues_j = sum_i p_ij g_i.
+    The backward recomputes the scores by the same chain and p from the saved lse; one pass owns the queries and one the rows of fy, every
+    sum runs in a fixed order (float32 with D <= 128: scores and gradient products on the matrix cores, in the tiles' register order;
+    otherwise the vector unit, in ascending index), every element is stored once: no atomics, no zero fill, the same bytes on every
+    run.  Nothing is read back
+    and every launch is on the current stream: a call on device tensors can sit in a captured graph, forward and backward.
+    """
+    what = "soft_match_features"
+    tau = _check_temperature(temperature, fx, what)
+    if not isinstance(return_best, bool):
+        raise ValueError("%s: return_best must be True or False, got %r" % (what, return_best))
+    code = _check_form(_form, fx, what)
+    form, by, _, ylens = _clouds.check(fy, y_rows, what, "fy", "y_rows", empty_ok=True, min_cols=1)
+    vform, bv, _, vlens = _clouds.check(values, None, what, "values", "y_rows", empty_ok=True, min_cols=1)
+    if vform != form:
+        raise ValueError("%s: values must have the form of fy (single tables, padded batches or lists), got %s and %s" % (what, vform, form))
+    if bv.dtype != by.dtype or bv.device != by.device:
+        raise ValueError("%s: values must have fy's dtype and device, got %s on %s" % (what, bv.dtype, bv.device))
+    if not (1 <= bv.shape[2] <= C_MAX):
+        raise ValueError("%s: values need C in [1, %d] columns, got %d" % (what, C_MAX, bv.shape[2]))
+    if tuple(bv.shape[:2]) != tuple(by.shape[:2]) or vlens != ylens:
+        raise ValueError("%s: values must hold one row per row of fy, got shape %s" % (what, tuple(bv.shape)))
+    form, on_cpu, lens, n, m, xb, yb, rx, ry = _clouds.pair_features(fx, fy, x_rows, y_rows, what, D_MAX)
+    _, vb, _ = _clouds.place(bv, None)
+    out, idx, prob = _SoftMatch.apply(xb, yb, vb, rx, ry, tau, code)
+    res = _clouds.restore(form, on_cpu, n, lens, [(ROW, out), (ROW, idx), (ROW, prob)])
+    return res if return_best else res[0]
 
 
 def _check_rules(mutual, ratio, max_d2, what):

@@ -1175,6 +1175,32 @@ int dicp_fpfh_spfh(int dtype, const void* points, int c, const void* normals, co
 int dicp_fpfh_combine(int dtype, const void* points, int c, const void* idx, int idx64, const int32_t* rows, int N, int m, int k, double radius,
                       const void* workspace, size_t workspace_bytes, void* out, void* stream);
 
+/* Soft descriptor matches (dicp_amd/match.py: soft_match_features; csrc/softmatch.hip, the rules: csrc/dicp_softmatch.h).  x (N,n,D) T,
+ * y (N,m,D) T, values (N,m,C) T, 1 <= D <= 256, 1 <= C <= 8, tau finite and > 0 with (T)(-2.0 / tau) finite and non-zero (DICP_ERR_SHAPE);
+ * x_rows / y_rows: optional (N) row counts as tgt_rows.  The score s_ij and the candidates of query i are dicp_knn_features', bit for bit.
+ * With c = (T)(-2.0 / tau):  l_ij = c s_ij,  p_ij = exp(l_ij - lse_i) over the candidates,  out_i = sum_j p_ij values_j: the softmax of
+ * -|x_i - y_j|^2 / tau.  Written: out (N,n,C) T, idx (N,n) int64 = the first candidate in (score, index) order (dicp_knn_features' k = 1),
+ * prob (N,n) T = p at idx, and lse (N,n) T, internal to the pair of calls.  A query at or past x_rows[b] or without a candidate gets a
+ * zero row, idx -1, prob 0 and lse +inf.  Rows of y at or past y_rows[b] enter nothing whatever they and their values hold; values are
+ * never examined.  Nothing is read back; no atomics: bit-reproducible per form.
+ *   form: DICP_MATCH_AUTO (float32: the scores on the matrix cores, float64: the vector unit), DICP_MATCH_VALU, DICP_MATCH_MFMA (float32
+ *   only: DICP_ERR_ENUM with float64).  The forms agree on idx exactly and on the sums to rounding (their orders of summation differ).
+ *   workspace: dicp_soft_match_workspace_bytes(dtype, N, m) bytes (0 for bad arguments; the table h), 16-byte aligned.
+ * dicp_soft_match_backward: from the cotangent grad_out (N,n,C) of out, with the SAME x, y, values, rows and tau and the out and lse the
+ *   forward wrote: delta_i = g_i . out_i, a_ij = p_ij (g_i . values_j - delta_i), p recomputed from the scores and lse;
+ *   grad_x[i,c] = -c sum_j a_ij y_jc;  grad_y[j,c] = c (y_jc sum_i a_ij - sum_i a_ij x_ic);  grad_values[j,k] = sum_i p_ij g_ik, every sum
+ *   sequential from +0.  Each of the three may be NULL.  Queries with lse = +inf and rows at or past the counts get exactly zero whatever
+ *   grad_out holds.  Every element is stored once: no zero fill, no atomics, bit-reproducible per form.
+ *   form: DICP_MATCH_AUTO (float32 with D <= 128: scores and gradient products on the matrix cores, the sums in the tiles' register order;
+ *   otherwise the vector unit, in ascending index), DICP_MATCH_VALU, DICP_MATCH_MFMA (DICP_ERR_ENUM with float64 or D > 128). */
+size_t dicp_soft_match_workspace_bytes(int dtype, int N, int m);
+int dicp_soft_match(int dtype, const void* x, const int32_t* x_rows, int n, const void* y, const int32_t* y_rows, int m, int D, int N,
+                    const void* values, int C, double tau, int form, void* out, void* lse, int64_t* idx, void* prob, void* workspace,
+                    size_t workspace_bytes, void* stream);
+int dicp_soft_match_backward(int dtype, const void* x, const int32_t* x_rows, int n, const void* y, const int32_t* y_rows, int m, int D, int N,
+                             const void* values, int C, double tau, int form, const void* out, const void* lse, const void* grad_out, void* grad_x,
+                             void* grad_y, void* grad_values, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
