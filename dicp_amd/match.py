@@ -14,8 +14,13 @@ and the same closed-form fit then makes the pose differentiable in both descript
     T0 = align_correspondences(x, soft, torch.arange(n).expand(N, n), weight=prob)
 
 All on the GPU (libdicp_hip.so: dicp_knn_features / _backward / _backward_det, dicp_soft_match / _backward, dicp_ransac_hypotheses /
-_score / _best, dicp_pair_residuals, and the Kabsch kernels of the ICP loop), without the (n, m) distance matrix; nothing is read back
-from the device.
+_score / _best, dicp_pair_residuals, dicp_compat_scores / _rank, and the Kabsch kernels of the ICP loop), without the (n, m) distance
+matrix; nothing is read back from the device.
+
+Between the matcher and RANSAC sits the pruning step for matches of which most are wrong (spatial compatibility, spectral matching):
+
+    idx_kept, score = prune_correspondences(x, y, idx, threshold=0.05, keep=256)    # the matches that keep their lengths to each other
+    T0, inliers = ransac_correspondences(x, y, idx_kept, 0.15, hypotheses=256)      # ... need far fewer hypotheses
 """
 import torch
 
@@ -427,25 +432,34 @@ def _residuals(xd, yd, idx32, rows, pose):
     return d2
 
 
+def _live_pairs(x0, y0, idx_d, rows):
+    """Rule 1 of ransac_correspondences on detached (N, n, 3) / (N, m, 3) points -> (idx32 (N, n), live (N, n) bool, pairs (N, n, 6): every
+    cloud's live rows (x[0:3], y[0:3]) packed first in ascending row order, P (N,) int32, index (N, n) int64: the row of every packed pair)"""
+    from .filter import _Select
+    N, n, _ = x0.shape
+    m, dev = y0.shape[1], x0.device
+    idx32 = _idx32(idx_d, m)
+    yg = torch.gather(y0, 1, idx32.clamp(min=0, max=m - 1).long()[..., None].expand(N, n, 3))
+    live = (idx32 >= 0) & torch.isfinite(x0).all(dim=-1) & torch.isfinite(yg).all(dim=-1)
+    if rows is not None:
+        live &= torch.arange(n, device=dev)[None, :] < rows[:, None]
+    pairs, P, index = _Select.apply(torch.cat((x0, yg), dim=-1).contiguous(), live.contiguous(), None, True)
+    return idx32, live, pairs, P, index
+
+
 def _ransac_stages(xd, yd, idx_d, weight, rows, threshold, hypotheses, seed, refine, _poses=None):
     """Every stage of ransac_correspondences on _pair_arguments' tensors, as a dict: live (N, n) bool, pairs (N, n, 6), P (N,) int32,
     index (N, n) int64, samples (N, H, 3) int32, poses (N, H, 12), counts (N, H) int32, best / best_count (N,) int32, pose_best (N, 12),
     thr2 (0-d), sets [I_0 .. I_R] of (N, n) bool, accepted [(N,) bool per round], round_poses [(N, 12) per round: T_j's pose], inliers (N, n)
     bool.  _poses (N, H, 12): the poses to
     score instead of stage 1's (samples are then -1).  Nothing is read back."""
-    from .filter import _Select
     N, n, _ = xd.shape
     m, dt, dev = yd.shape[1], xd.dtype, xd.device
     code = _DT[dt]
     H = int(hypotheses)
     with torch.no_grad():
         x0, y0 = xd.detach(), yd.detach()
-        idx32 = _idx32(idx_d, m)
-        yg = torch.gather(y0, 1, idx32.clamp(min=0, max=m - 1).long()[..., None].expand(N, n, 3))
-        live = (idx32 >= 0) & torch.isfinite(x0).all(dim=-1) & torch.isfinite(yg).all(dim=-1)
-        if rows is not None:
-            live &= torch.arange(n, device=dev)[None, :] < rows[:, None]
-        pairs, P, index = _Select.apply(torch.cat((x0, yg), dim=-1).contiguous(), live.contiguous(), None, True)
+        idx32, live, pairs, P, index = _live_pairs(x0, y0, idx_d, rows)
         if _poses is None:
             poses = torch.empty((N, H, 12), dtype=dt, device=dev)
             samples = torch.empty((N, H, 3), dtype=torch.int32, device=dev)
@@ -558,3 +572,107 @@ def correspondence_residuals(x, y, idx, T, x_rows=None):
     if on_cpu:
         d2 = d2.cpu()
     return d2[0] if form == "single" else d2
+
+
+ITER_MAX = 64           # COMPAT_ITER_MAX (csrc/dicp_compat.h)
+
+
+def _check_compat(threshold, iterations, min_length, what):
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float)) or not (0.0 < float(threshold) < float("inf")):
+        raise ValueError("%s: threshold must be a finite number > 0, got %r" % (what, threshold))
+    if isinstance(min_length, bool) or not isinstance(min_length, (int, float)) or not (0.0 <= float(min_length) < float("inf")):
+        raise ValueError("%s: min_length must be a finite number >= 0, got %r" % (what, min_length))
+    if isinstance(iterations, bool) or not isinstance(iterations, int) or not (0 <= iterations <= ITER_MAX):
+        raise ValueError("%s: iterations must be an int in [0, %d], got %r" % (what, ITER_MAX, iterations))
+
+
+def _compat_stages(xd, yd, idx_d, rows, threshold, iterations, min_length, keep=None):
+    """correspondence_compatibility (and, with keep, prune_correspondences) on _pair_arguments' tensors, as a dict: live (N, n) bool,
+    pairs (N, n, 6), P (N,) int32, index (N, n) int64, score_packed (N, n) T and degree_packed (N, n) int32 (0 at and past P), score and
+    degree in the original row order; with keep also rank_packed (N, n) int32, kept (N, n) bool and idx_kept.  Nothing is read back."""
+    N, n, _ = xd.shape
+    dt, dev = xd.dtype, xd.device
+    code = _DT[dt]
+    it = int(iterations)
+    with torch.no_grad():
+        idx32, live, pairs, P, index = _live_pairs(xd.detach(), yd.detach(), idx_d, rows)
+        w = torch.empty((2, N, n), dtype=dt, device=dev)
+        wmax = torch.zeros((max(it, 1), N), dtype=torch.int32 if dt == torch.float32 else torch.int64, device=dev)   # (the kernels take integer maxima)
+        sp = torch.empty((N, n), dtype=dt, device=dev)
+        dp = torch.empty((N, n), dtype=torch.int32, device=dev)
+        _lib.call("dicp_compat_scores", dev, code, _p(pairs), _p(P), N, n, it, float(threshold), float(min_length), _p(w), _p(wmax), _p(sp), _p(dp))
+        pos = (torch.cumsum(live, dim=1) - 1).clamp(min=0)                  # the packed position of every live row
+        score = torch.where(live, torch.gather(sp, 1, pos), torch.zeros((), dtype=dt, device=dev))
+        degree = torch.where(live, torch.gather(dp, 1, pos), torch.zeros((), dtype=torch.int32, device=dev))
+        st = dict(live=live, pairs=pairs, P=P, index=index, score_packed=sp, degree_packed=dp, score=score, degree=degree)
+        if keep is not None:
+            rank = torch.empty((N, n), dtype=torch.int32, device=dev)
+            _lib.call("dicp_compat_rank", dev, code, _p(sp), _p(P), N, n, _p(rank))
+            kept = live & (torch.gather(rank, 1, pos) < min(int(keep), 0x7fffffff))
+            st.update(rank_packed=rank, kept=kept, idx_kept=torch.where(kept, idx_d, torch.full_like(idx_d, -1)))
+    return st
+
+
+def _compat_outputs(form, on_cpu, outs):
+    if on_cpu:
+        outs = [t.cpu() for t in outs]
+    return tuple(t[0] if form == "single" else t for t in outs)
+
+
+def correspondence_compatibility(x, y, idx, threshold, iterations=10, min_length=0.0, x_rows=None):
+    """The spatial-compatibility score and degree of every correspondence: which matches keep their lengths to each other, as all correct
+    matches do under a rigid motion and wrong ones only by accident (spectral matching; the first-order compatibility of SC2-PCR / PointDSC).
+
+    x, y, idx, x_rows: exactly as align_correspondences / ransac_correspondences (single clouds or padded batches, float32 or float64,
+        columns 0:3, idx int32 or int64 with negative = no match; CPU tensors are computed on the GPU and returned on the CPU).
+    threshold: a finite number > 0, the largest change of a length.  min_length: a finite number >= 0.  iterations: an int in [0, 64].
+    Anything else is a ValueError before any device work.
+
+    Definition (hardware-independent; T the points' dtype, fma its correctly rounded fused multiply-add, sqrt and / correctly rounded):
+     1. The live pairs are those of rule 1 of ransac_correspondences, packed in ascending row order: P per cloud, (x_p, y_p) each.
+     2. Packed positions p != q are compatible iff |e| <= thr and a >= L and b >= L, thr = T(threshold), L = T(min_length), where
+            A = +0, A = fma(t_a, t_a, A) for a = 0, 1, 2 with t_a = x_pa - x_qa;  B likewise from y;  a = sqrt(A), b = sqrt(B), e = a - b.
+        Every comparison with a NaN is false.  The relation is symmetric bit for bit.  With min_length > 0, matches that share a source or a
+        target point stop vouching for each other.
+     3. degree_p = the number of q != p below P compatible with p.
+     4. v^0 = 1.  For t = 1 .. iterations: w_p = the sum over q = 0 .. P - 1 in ascending q of v^{t-1}_q over the q compatible with p or equal
+        to p (the matrix M + I: the same eigenvectors, no oscillation), added sequentially in T from +0, one rounding per addition;
+        wmax = max_p w_p (>= 1 whenever P >= 1);  v^t_p = w_p / wmax.  score = v^iterations: the power iteration towards the leading
+        eigenvector, normalised to a maximum of 1.  w^1 = degree + 1 exactly for P < 2^24; iterations = 0 gives score 1 on the live rows.
+
+    Returns (score, degree): (N, n) or (n,), score in x's dtype and degree int32, in the original row order, 0 on rows that are not live.
+    Neither requires grad: they are decisions.  Nothing is read back and no launch shape depends on device data: a call on device tensors
+    can sit in a captured graph.  No float atomics: the same bytes on every run.
+
+    Kernels (libdicp_hip.so): dicp_select_rows packs the live pairs; dicp_compat_scores runs one pass over all P^2 pairs per iteration, a
+    lane per row p walking q in LDS tiles, O(n) memory per cloud.
+    """
+    what = "correspondence_compatibility"
+    _check_compat(threshold, iterations, min_length, what)
+    form, on_cpu, xd, yd, idx_d, _, rows = _pair_arguments(x, y, idx, None, x_rows, what)
+    st = _compat_stages(xd, yd, idx_d, rows, threshold, iterations, min_length)
+    return _compat_outputs(form, on_cpu, [st["score"], st["degree"]])
+
+
+def prune_correspondences(x, y, idx, threshold, keep, iterations=10, min_length=0.0, x_rows=None):
+    """The `keep` most compatible correspondences of every cloud: the step between match_features and ransac_correspondences when most of
+    the matches are wrong.
+
+    x, y, idx, threshold, iterations, min_length, x_rows: as correspondence_compatibility.  keep: an int >= 1 (anything else is a ValueError
+    before any device work).
+
+     5. With score of correspondence_compatibility, the rank of live pair p is the number of live q with score_q > score_p, or
+        score_q == score_p and q < p; a pair is kept iff its rank < keep.  keep >= P keeps every live pair.
+
+    Returns (idx_kept, score): idx_kept has idx's dtype and shape, idx where the row is kept and -1 elsewhere -- it feeds
+    align_correspondences / ransac_correspondences / correspondence_residuals unchanged; score as correspondence_compatibility's.  No
+    gradient, nothing read back, bit-reproducible, fit for a captured graph.  Kernels: those of correspondence_compatibility and
+    dicp_compat_rank, a second, much cheaper pass over the P^2 pairs.
+    """
+    what = "prune_correspondences"
+    _check_compat(threshold, iterations, min_length, what)
+    if isinstance(keep, bool) or not isinstance(keep, int) or keep < 1:
+        raise ValueError("%s: keep must be an int >= 1, got %r" % (what, keep))
+    form, on_cpu, xd, yd, idx_d, _, rows = _pair_arguments(x, y, idx, None, x_rows, what)
+    st = _compat_stages(xd, yd, idx_d, rows, threshold, iterations, min_length, keep=keep)
+    return _compat_outputs(form, on_cpu, [st["idx_kept"], st["score"]])

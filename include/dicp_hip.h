@@ -1153,6 +1153,24 @@ int dicp_ransac_best(int dtype, const int32_t* counts, const void* poses, const 
 int dicp_pair_residuals(int dtype, const void* x, const void* y, const int32_t* idx, const int32_t* x_rows, const void* pose, int N, int n, int m,
                         void* d2, void* stream);
 
+/* Spatial compatibility of correspondences (dicp_amd/match.py: correspondence_compatibility / prune_correspondences; csrc/compat.hip, the
+ * rules: csrc/dicp_compat.h).  pairs (N,n,6) T and P (N) int32 as for RANSAC above.  thr = T(threshold), L = T(min_length); threshold finite
+ * and > 0, min_length finite and >= 0, 0 <= iterations <= 64 (DICP_ERR_SHAPE).  fma, sqrt and / are the correctly rounded ones of T.
+ * Nothing is read back; no float atomics: every output is bit-reproducible.
+ *   Packed positions p != q below P are compatible iff |e| <= thr and a >= L and b >= L with A = +0, A = fma(t_a, t_a, A) over a = 0, 1, 2,
+ *   t_a = x_pa - x_qa, B likewise from y, a = sqrt(A), b = sqrt(B), e = a - b; a comparison with a NaN is false.
+ * dicp_compat_scores: degree (N,n) int32 = the number of q != p below P compatible with p; score (N,n) T = v^iterations with v^0 = 1,
+ *   w_p = the sum over q = 0 .. P - 1 in ascending q, sequential in T from +0, of v_q over the q compatible with p or equal to p,
+ *   v_p = w_p / max_p w_p.  Both in PACKED order, 0 at and past P.  One launch per iteration (one for iterations = 0) and one more; a
+ *   workgroup takes `rows` rows p and walks q in LDS tiles of `tile` rows (dicp_compat_geometry).  Scratch, both written here: w (2,N,n) T;
+ *   wmax (max(iterations, 1), N) of T's size, which the CALLER zeroes first (the maxima are integer atomics on the sums' bits).
+ * dicp_compat_rank: rank (N,n) int32 = the number of q below P with score_q > score_p, or score_q == score_p and q < p, for p < P and
+ *   INT32_MAX at and past P; score (N,n) T is dicp_compat_scores' (packed). */
+void dicp_compat_geometry(int* rows, int* tile);
+int dicp_compat_scores(int dtype, const void* pairs, const int32_t* P, int N, int n, int iterations, double threshold, double min_length, void* w,
+                       void* wmax, void* score, int32_t* degree, void* stream);
+int dicp_compat_rank(int dtype, const void* score, const int32_t* P, int N, int n, int32_t* rank, void* stream);
+
 /* FPFH descriptors, 33 channels (dicp_amd/fpfh.py: fpfh_features / compute_fpfh; csrc/fpfh.hip, the rules: csrc/dicp_fpfh.h).  points
  * (N,m,c) T with c >= 3 (columns 0:3 are read), normals (N,m,3) T, idx (N,m,k) int64 (idx64 = 1) or int32 (idx64 = 0; anything else:
  * DICP_ERR_ENUM), a search of every cloud against ITSELF with 1 <= k <= 32; rows: optional (N) row counts.  radius: 0 for none, otherwise
