@@ -99,8 +99,12 @@ class ICP:
         trim_dist : None or a distance; loss_fn : None or {"name": "huber"|"cauchy"|"trim", "metric": x}
         dim : 3, or 2 to optimise rotation about z and translation in x,y only
         source_rows, target_rows (build-specific, optional): (N) row counts of a PADDED batch (N,n,3|6) / (N,m,3|6) -- ragged clouds without Python lists: rows
-                 past a cloud's count take no part (whatever they hold; with Gumbel-softmax correspondences too: they enter no softmax and get
-                 zero gradient), as if the clouds had been given as a list of their own lengths.  A list of 256
+                 past a cloud's count take no part (whatever they hold -- NaN and inf included, and so the entries of `weight` past source_rows; with
+                 Gumbel-softmax correspondences too: they enter no softmax and get zero gradient), as if the clouds had been given as a list of
+                 their own lengths: every result of a cloud's own rows, its statistics (an (N,1) weight counts against the cloud's own rows) and
+                 its gradients; the gradient to a pad row or a weight's pad entry is exactly 0.  Of the results' own pad rows, "weights" holds 0
+                 in every iteration and "pc" holds the pad row itself under the final pose (NaN for a NaN row): an output of no meaning, whose
+                 cotangent is not read.  A list of 256
                  clouds is 512 leaf tensors to autograd, ~8 ms of host time per call; the padded batch is one
         returns {"pc" (N,n,3), "T" (N,4,4), "costs" (N,K,1), "deltas" (N,K,6,1),
                  "weights" (N,K,n*r,1), "stats": {"converged","iterations","matched_ratio"}}
@@ -134,8 +138,9 @@ class ICP:
                 raise ValueError("source_rows / target_rows describe a padded batch: not together with lists of clouds")
             src_rows, tgt_rows = self._given_rows(source_rows, source, "source_rows"), self._given_rows(target_rows, target, "target_rows")
             if src_rows is not None:      # the rows past a cloud's own carry weight zero, like the pads of a list (ICP.py:386-398)
-                live = (torch.arange(source.shape[1], device=dev)[None, :] < src_rows[:, None]).to(source.dtype)
-                w_pts = live if w_pts is None else w_pts * live
+                live = torch.arange(source.shape[1], device=dev)[None, :] < src_rows[:, None]
+                # (selected, not multiplied: a NaN or inf in a weight's pad entry is 0 here and its gradient is 0, not NaN x 0)
+                w_pts = live.to(source.dtype) if w_pts is None else torch.where(live, w_pts, torch.zeros((), dtype=w_pts.dtype, device=dev))
 
         if dim == 2:                                                                     # ICP.py:107-116
             # (the masks are made once per dtype and device: a host-to-device copy per call cannot be captured into a hipGraph -- the reference's own
@@ -190,7 +195,8 @@ class ICP:
             # an (N,1) weight stays (N,1) in the reference, so its "matches at the start" (ICP.py:248,269: sum over dim 1 of
             # w_init > thresh) counts ONE per cloud where the kernels, handed the expanded (N,n) tensor, count n: same
             # numerator, the reference's denominator (the kernels' ratio is float32(int / int): the integer is recovered exactly)
-            n_pts = float(source.shape[1])
+            # (with row counts the kernels' denominator is the cloud's own count: the weight is zero past it)
+            n_pts = float(source.shape[1]) if src_rows is None else src_rows.to(matched.dtype)
             on = (w_pts[:, 0] > self.match_ratio_thresh) & (matched > 0)
             matched = torch.where(on, torch.round(matched * n_pts), matched)
         if self.verbose:                                                                 # ICP.py:262-264

@@ -817,9 +817,15 @@ def _bwd_begin(ctx, gT, gpc):
 def _bwd_pc_cotangent(B, gT, gpc):
     B.gsrc_pc = None
     if gpc is not None:
-        B.gsrc_pc = torch.empty_like(B.src)
+        rows = B.cfg.src_rows
+        # (row counts: the pad rows of pc are outputs of no meaning -- their cotangent is not read, nor the pads themselves: 0 x NaN would reach the pose)
+        B.gsrc_pc = torch.empty_like(B.src) if rows is None else torch.zeros_like(B.src)
         pcp = torch.empty((B.N, B.lib.dicp_accumulate_blocks(B.n), _lib.NBWD_PAD), dtype=B.dt, device=B.dev)
-        _lib.check(B.lib.dicp_transform_points_bwd(B.code, _p(B.src), _p(B.poses[B.K]), _p(gpc.contiguous()), _p(B.gsrc_pc), _p(pcp), B.N, B.n, B.st), "dicp_transform_points_bwd")
+        if rows is None:
+            _lib.check(B.lib.dicp_transform_points_bwd(B.code, _p(B.src), _p(B.poses[B.K]), _p(gpc.contiguous()), _p(B.gsrc_pc), _p(pcp), B.N, B.n, B.st), "dicp_transform_points_bwd")
+        else:
+            _lib.check(B.lib.dicp_transform_points_bwd_rows(B.code, _p(B.src), _p(B.poses[B.K]), _p(gpc.contiguous()), _p(B.gsrc_pc), _p(pcp), _p(rows), B.N, B.n, B.st),
+                       "dicp_transform_points_bwd_rows")
         gT_pc = _pose_sums_to_gT(pcp, B.N, B.dt, B.dev, B.st)
         gT = gT_pc if gT is None else gT + gT_pc
     return gT

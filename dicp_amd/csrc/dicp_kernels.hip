@@ -1204,6 +1204,10 @@ int dicp_transform_points_bwd(int dtype, const void* src, const void* pose, cons
                               int N, int n, void* stream) {
     return transform_points_bwd_go(dtype, src, pose, gout, gsrc, partials, N, n, 0, stream);
 }
+int dicp_transform_points_bwd_rows(int dtype, const void* src, const void* pose, const void* gout, void* gsrc, void* partials,
+                                   const int32_t* src_rows, int N, int n, void* stream) {
+    return transform_points_bwd_go(dtype, src, pose, gout, gsrc, partials, N, n, 0, stream, src_rows);
+}
 static int transform_points_bwd_go(int dtype, const void* src, const void* pose, const void* gout, void* gsrc, void* partials, int N, int n, int add, void* stream,
                                    const int32_t* src_rows) {
     if (!src || !pose || !gout || !partials) return DICP_ERR_NULL;

@@ -674,6 +674,10 @@ int dicp_kabsch_bwd(int dtype, const void* src, const void* tgt, int c, const in
 int dicp_transform_points(int dtype, const void* src, const void* pose, void* out, int N, int n, void* stream);
 int dicp_transform_points_bwd(int dtype, const void* src, const void* pose, const void* gout, void* gsrc, void* partials,
                               int N, int n, void* stream);
+/* ... of a padded batch with row counts: src_rows (N) device int32 or NULL (every row).  Rows past a cloud's count are not read -- neither src nor
+ * gout: a NaN there reaches nothing -- and their rows of gsrc are NOT written (the caller hands in zeros). */
+int dicp_transform_points_bwd_rows(int dtype, const void* src, const void* pose, const void* gout, void* gsrc, void* partials,
+                                   const int32_t* src_rows, int N, int n, void* stream);
 
 /* loss(name, metric, differentiable, tanh_steepness).get_weight(err), loss.py:11-58, for
  * callers that use the class directly.  err (rows,r), r in {1,3}; w (rows). */

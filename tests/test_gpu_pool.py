@@ -280,7 +280,9 @@ def _grad_case(f, idx, rows, reduce, seed, nan_at_empty=False):
     ref = torch.zeros(N * m * C, dtype=torch.float64, device="cuda").index_add_(0, flat, t).reshape(N * m, C)
     ab = torch.zeros(N * m * C, dtype=torch.float64, device="cuda").index_add_(0, flat, t.abs()).reshape(N * m, C)
     deg = torch.zeros(N * m, dtype=torch.float64, device="cuda").index_add_(0, (safe + bi * m).reshape(-1), live.reshape(-1).double())[:, None]
-    assert torch.allclose(fa.grad.reshape(N * m, C), ref, rtol=1e-11, atol=1e-13)
+    # (scaffolding only: both sides are torch's own float64 sums of the same `deg` terms, added with atomics in an order that changes from run to run; each is
+    #  within (deg - 1) 2^-53 sum|terms| of the exact sum, so any two orders agree elementwise within twice that)
+    assert ((fa.grad.reshape(N * m, C) - ref).abs() <= 2 * deg * 2.0 ** -53 * ab).all()
     assert torch.isfinite(got).all()
     assert (got[(deg == 0).expand_as(got)] == 0).all() and ((deg == 0).any() or m == 1)
     bound = (deg + k + 8) * u * ab

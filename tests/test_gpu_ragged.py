@@ -160,9 +160,14 @@ def test_lists_are_packed_by_one_launch_like_pad_sequence():
     assert _ops.packable(views, (6,)) and torch.equal(_ops.pack_list(views, 6), torch.nn.utils.rnn.pad_sequence(views, batch_first=True))
     # the launch reads the clouds through raw pointers: a cloud of another dtype, too few columns or a strided column is refused by pack_list itself
     base = torch.randn((10, 6), generator=g, dtype=torch.float32).cuda()
-    for bad in ([base, base.double()], [base[:, :2]], [base.t().contiguous().t()], [base, base.cpu()], [base.reshape(2, 5, 6)]):
+    # (a ONE-row cloud is no exception to the column stride: x[:1, ::2] would be read as three consecutive elements; an empty cloud is refused as packable does)
+    for bad in ([base, base.double()], [base[:, :2]], [base.t().contiguous().t()], [base, base.cpu()], [base.reshape(2, 5, 6)], [base[:1, ::2]], [base, base[:1, ::2]],
+                [base, base[:0]]):
         with pytest.raises(ValueError):
             _ops.pack_list(bad, 3)
+    # ... and its row stride says nothing (there is no second row): a valid one-row cloud whose stride(0) < shape[1] is taken
+    one = torch.as_strided(base, (1, 6), (1, 1))
+    assert one.stride(0) < one.shape[1] and torch.equal(_ops.pack_list([base, one], 6), torch.nn.utils.rnn.pad_sequence([base, one], batch_first=True))
     assert not _ops.packable([c.detach().t() for c in clouds], (6,)) and not _ops.packable([c.detach().cpu() for c in clouds], (6,))
 
 
