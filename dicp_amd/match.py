@@ -14,13 +14,20 @@ and the same closed-form fit then makes the pose differentiable in both descript
     T0 = align_correspondences(x, soft, torch.arange(n).expand(N, n), weight=prob)
 
 All on the GPU (libdicp_hip.so: dicp_knn_features / _backward / _backward_det, dicp_soft_match / _backward, dicp_ransac_hypotheses /
-_score / _best, dicp_pair_residuals, dicp_compat_scores / _rank, and the Kabsch kernels of the ICP loop), without the (n, m) distance
+_score / _best, dicp_pair_residuals, dicp_compat_scores / _rank, dicp_compat2_bits / _common / _rank / _seeds, and the Kabsch kernels of the ICP loop), without the (n, m) distance
 matrix; nothing is read back from the device.
 
 Between the matcher and RANSAC sits the pruning step for matches of which most are wrong (spatial compatibility, spectral matching):
 
     idx_kept, score = prune_correspondences(x, y, idx, threshold=0.05, keep=256)    # the matches that keep their lengths to each other
     T0, inliers = ransac_correspondences(x, y, idx_kept, 0.15, hypotheses=256)      # ... need far fewer hypotheses
+
+When only a handful of the matches are right, the second-order measure (SC2: triangles of compatible matches, on packed adjacency bits)
+separates them in one pass, and its best matches seed the hypotheses instead of random triples:
+
+    score2, degree2, degree = second_order_compatibility(x, y, idx, threshold=0.05)
+    idx_kept, score2 = prune_correspondences(x, y, idx, threshold=0.05, keep=256, order=2)
+    T0, inliers = consensus_correspondences(x, y, idx, threshold=0.05, seeds=64, members=16)
 """
 import torch
 
@@ -447,6 +454,40 @@ def _live_pairs(x0, y0, idx_d, rows):
     return idx32, live, pairs, P, index
 
 
+def _score_and_refine(x0, y0, idx_d, idx32, weight, rows, pairs, P, poses, threshold, refine, real=None):
+    """The stages ransac_correspondences and consensus_correspondences share, from a cloud's hypothesis poses (N, H, 12) on (under
+    torch.no_grad, on detached points): dicp_ransac_score, dicp_ransac_best, I_0 and the LO rounds -> (counts, best, best_count, pose_best,
+    thr2, sets, accepted, round_poses, inliers).  real (N, H) bool: the hypotheses that exist; the counts of the others are zeroed before
+    the choice."""
+    N, n, _ = x0.shape
+    dt, dev = x0.dtype, x0.device
+    code = _DT[dt]
+    H = poses.shape[1]
+    counts = torch.empty((N, H), dtype=torch.int32, device=dev)
+    _lib.call("dicp_zero", dev, _p(counts), counts.numel() * 4)
+    _lib.call("dicp_ransac_score", dev, code, _p(pairs), _p(P), _p(poses), N, n, H, float(threshold), _p(counts))
+    if real is not None:
+        counts = torch.where(real, counts, torch.zeros((), dtype=torch.int32, device=dev)).contiguous()
+    best = torch.empty((N,), dtype=torch.int32, device=dev)
+    best_count = torch.empty((N,), dtype=torch.int32, device=dev)
+    pose_best = torch.empty((N, 12), dtype=dt, device=dev)
+    _lib.call("dicp_ransac_best", dev, code, _p(counts), _p(poses), _p(P), N, H, _p(best), _p(best_count), _p(pose_best))
+    thr2 = torch.full((), float(threshold) * float(threshold), dtype=dt, device=dev)        # (the product in double, rounded once to T)
+    some = (P >= 3)[:, None]
+    inl = (_residuals(x0, y0, idx32, rows, pose_best) <= thr2) & some
+    sets, accepted, round_poses = [inl], [], []
+    minus = torch.full_like(idx_d, -1)
+    for _ in range(int(refine)):
+        pj = _pose12(_align(x0, y0, torch.where(inl, idx_d, minus), weight if weight is None else weight.detach(), rows))
+        round_poses.append(pj)
+        new = (_residuals(x0, y0, idx32, rows, pj) <= thr2) & some
+        ok = new.sum(dim=1) >= inl.sum(dim=1)
+        inl = torch.where(ok[:, None], new, inl)
+        sets.append(inl)
+        accepted.append(ok)
+    return counts, best, best_count, pose_best, thr2, sets, accepted, round_poses, inl
+
+
 def _ransac_stages(xd, yd, idx_d, weight, rows, threshold, hypotheses, seed, refine, _poses=None):
     """Every stage of ransac_correspondences on _pair_arguments' tensors, as a dict: live (N, n) bool, pairs (N, n, 6), P (N,) int32,
     index (N, n) int64, samples (N, H, 3) int32, poses (N, H, 12), counts (N, H) int32, best / best_count (N,) int32, pose_best (N, 12),
@@ -454,7 +495,7 @@ def _ransac_stages(xd, yd, idx_d, weight, rows, threshold, hypotheses, seed, ref
     bool.  _poses (N, H, 12): the poses to
     score instead of stage 1's (samples are then -1).  Nothing is read back."""
     N, n, _ = xd.shape
-    m, dt, dev = yd.shape[1], xd.dtype, xd.device
+    dt, dev = xd.dtype, xd.device
     code = _DT[dt]
     H = int(hypotheses)
     with torch.no_grad():
@@ -467,26 +508,8 @@ def _ransac_stages(xd, yd, idx_d, weight, rows, threshold, hypotheses, seed, ref
         else:
             poses = _poses.to(device=dev, dtype=dt).reshape(N, H, 12).contiguous()
             samples = torch.full((N, H, 3), -1, dtype=torch.int32, device=dev)
-        counts = torch.empty((N, H), dtype=torch.int32, device=dev)
-        _lib.call("dicp_zero", dev, _p(counts), counts.numel() * 4)
-        _lib.call("dicp_ransac_score", dev, code, _p(pairs), _p(P), _p(poses), N, n, H, float(threshold), _p(counts))
-        best = torch.empty((N,), dtype=torch.int32, device=dev)
-        best_count = torch.empty((N,), dtype=torch.int32, device=dev)
-        pose_best = torch.empty((N, 12), dtype=dt, device=dev)
-        _lib.call("dicp_ransac_best", dev, code, _p(counts), _p(poses), _p(P), N, H, _p(best), _p(best_count), _p(pose_best))
-        thr2 = torch.full((), float(threshold) * float(threshold), dtype=dt, device=dev)        # (the product in double, rounded once to T)
-        some = (P >= 3)[:, None]
-        inl = (_residuals(x0, y0, idx32, rows, pose_best) <= thr2) & some
-        sets, accepted, round_poses = [inl], [], []
-        minus = torch.full_like(idx_d, -1)
-        for _ in range(int(refine)):
-            pj = _pose12(_align(x0, y0, torch.where(inl, idx_d, minus), weight if weight is None else weight.detach(), rows))
-            round_poses.append(pj)
-            new = (_residuals(x0, y0, idx32, rows, pj) <= thr2) & some
-            ok = new.sum(dim=1) >= inl.sum(dim=1)
-            inl = torch.where(ok[:, None], new, inl)
-            sets.append(inl)
-            accepted.append(ok)
+        counts, best, best_count, pose_best, thr2, sets, accepted, round_poses, inl = _score_and_refine(
+            x0, y0, idx_d, idx32, weight, rows, pairs, P, poses, threshold, refine)
     return dict(live=live, pairs=pairs, P=P, index=index, samples=samples, poses=poses, counts=counts, best=best, best_count=best_count,
                 pose_best=pose_best, thr2=thr2, sets=sets, accepted=accepted, round_poses=round_poses, inliers=inl)
 
@@ -654,25 +677,195 @@ def correspondence_compatibility(x, y, idx, threshold, iterations=10, min_length
     return _compat_outputs(form, on_cpu, [st["score"], st["degree"]])
 
 
-def prune_correspondences(x, y, idx, threshold, keep, iterations=10, min_length=0.0, x_rows=None):
+def prune_correspondences(x, y, idx, threshold, keep, iterations=10, min_length=0.0, x_rows=None, order=1):
     """The `keep` most compatible correspondences of every cloud: the step between match_features and ransac_correspondences when most of
     the matches are wrong.
 
-    x, y, idx, threshold, iterations, min_length, x_rows: as correspondence_compatibility.  keep: an int >= 1 (anything else is a ValueError
-    before any device work).
+    x, y, idx, threshold, iterations, min_length, x_rows: as correspondence_compatibility.  keep: an int >= 1; order: 1 or 2 (anything else
+    is a ValueError before any device work).
 
      5. With score of correspondence_compatibility, the rank of live pair p is the number of live q with score_q > score_p, or
         score_q == score_p and q < p; a pair is kept iff its rank < keep.  keep >= P keeps every live pair.
 
+    order=2 ranks by the second-order degree instead (rules 6-8 of second_order_compatibility: a pair is kept iff rank2 < keep), ignores
+    `iterations` and returns score2 as score: one pass that separates better than the ten first-order passes when the inliers are few,
+    at O(n^2 / 8) bytes per cloud.
+
     Returns (idx_kept, score): idx_kept has idx's dtype and shape, idx where the row is kept and -1 elsewhere -- it feeds
     align_correspondences / ransac_correspondences / correspondence_residuals unchanged; score as correspondence_compatibility's.  No
     gradient, nothing read back, bit-reproducible, fit for a captured graph.  Kernels: those of correspondence_compatibility and
-    dicp_compat_rank, a second, much cheaper pass over the P^2 pairs.
+    dicp_compat_rank, a second, much cheaper pass over the P^2 pairs; order=2: those of second_order_compatibility.
     """
     what = "prune_correspondences"
     _check_compat(threshold, iterations, min_length, what)
     if isinstance(keep, bool) or not isinstance(keep, int) or keep < 1:
         raise ValueError("%s: keep must be an int >= 1, got %r" % (what, keep))
+    if isinstance(order, bool) or order not in (1, 2):
+        raise ValueError("%s: order must be 1 or 2, got %r" % (what, order))
     form, on_cpu, xd, yd, idx_d, _, rows = _pair_arguments(x, y, idx, None, x_rows, what)
+    if order == 2:
+        st = _compat2_stages(xd, yd, idx_d, rows, threshold, min_length, keep=keep)
+        return _compat_outputs(form, on_cpu, [st["idx_kept"], st["score2"]])
     st = _compat_stages(xd, yd, idx_d, rows, threshold, iterations, min_length, keep=keep)
     return _compat_outputs(form, on_cpu, [st["idx_kept"], st["score"]])
+
+
+N2_MAX = 1 << 20        # COMPAT2_N_MAX (csrc/dicp_compat2.h)
+MEMBERS_MIN, MEMBERS_MAX = 3, 32
+
+
+def _compat2_stages(xd, yd, idx_d, rows, threshold, min_length, keep=None, seeds=None, members=None):
+    """second_order_compatibility (with keep, prune_correspondences(order=2); with seeds and members, the hypotheses of
+    consensus_correspondences) on _pair_arguments' tensors, as a dict: idx32, live (N, n) bool, pairs (N, n, 6), P (N,) int32, index,
+    adj (N, n, W) int64, degree_packed (N, n) int32, degree2_packed (N, n) int64, rank2_packed (N, n) int32, score2_packed (N, n) T, and
+    score2 / degree2 / degree in the original row order; with keep also kept and idx_kept; with seeds also seedpos (N, seeds) int32 (only
+    the entries below min(seeds, P) are written), members (N, seeds, members) int32, poses (N, seeds, 12) T and real (N, seeds) bool.
+    Nothing is read back."""
+    N, n, _ = xd.shape
+    dt, dev = xd.dtype, xd.device
+    code = _DT[dt]
+    if n > N2_MAX or N * n * ((n + 63) // 64) >= 1 << 40:
+        raise ValueError("second-order compatibility: %d clouds of %d rows need %d bytes of adjacency bits: too many" % (N, n, N * n * ((n + 63) // 64) * 8))
+    W = (n + 63) // 64
+    H = 0 if seeds is None else int(seeds)
+    with torch.no_grad():
+        idx32, live, pairs, P, index = _live_pairs(xd.detach(), yd.detach(), idx_d, rows)
+        adj = torch.empty((N, n, W), dtype=torch.int64, device=dev)
+        dp = torch.empty((N, n), dtype=torch.int32, device=dev)
+        d2p = torch.empty((N, n), dtype=torch.int64, device=dev)
+        rank = torch.empty((N, n), dtype=torch.int32, device=dev)
+        s2p = torch.empty((N, n), dtype=dt, device=dev)
+        seedpos = torch.empty((N, H), dtype=torch.int32, device=dev) if H else None
+        _lib.call("dicp_compat2_bits", dev, code, _p(pairs), _p(P), N, n, float(threshold), float(min_length), _p(adj), _p(dp), _p(d2p))
+        _lib.call("dicp_compat2_common", dev, _p(adj), _p(P), N, n, _p(d2p))
+        _lib.call("dicp_compat2_rank", dev, code, _p(d2p), _p(P), N, n, H, _p(rank), _p(s2p), _p(seedpos))
+        pos = (torch.cumsum(live, dim=1) - 1).clamp(min=0)                  # the packed position of every live row
+        score2 = torch.where(live, torch.gather(s2p, 1, pos), torch.zeros((), dtype=dt, device=dev))
+        degree2 = torch.where(live, torch.gather(d2p, 1, pos), torch.zeros((), dtype=torch.int64, device=dev))
+        degree = torch.where(live, torch.gather(dp, 1, pos), torch.zeros((), dtype=torch.int32, device=dev))
+        st = dict(idx32=idx32, live=live, pairs=pairs, P=P, index=index, adj=adj, degree_packed=dp, degree2_packed=d2p, rank2_packed=rank,
+                  score2_packed=s2p, score2=score2, degree2=degree2, degree=degree)
+        if keep is not None:
+            kept = live & (torch.gather(rank, 1, pos) < min(int(keep), 0x7fffffff))
+            st.update(kept=kept, idx_kept=torch.where(kept, idx_d, torch.full_like(idx_d, -1)))
+        if H:
+            K = int(members)
+            mem = torch.empty((N, H, K), dtype=torch.int32, device=dev)
+            poses = torch.empty((N, H, 12), dtype=dt, device=dev)
+            _lib.call("dicp_compat2_seeds", dev, code, _p(pairs), _p(P), _p(adj), _p(seedpos), N, n, H, K, _p(mem), _p(poses))
+            st.update(seedpos=seedpos, members=mem, poses=poses, real=mem[:, :, 2] >= 0)
+    return st
+
+
+def _check_compat2(threshold, min_length, what):
+    _check_compat(threshold, 0, min_length, what)
+
+
+def second_order_compatibility(x, y, idx, threshold, min_length=0.0, x_rows=None, return_adjacency=False):
+    """The second-order spatial compatibility (SC2) of every correspondence: how many triangles of mutually compatible matches pass
+    through it.  Two correct matches share every other correct match as a common compatible neighbour; a wrong match compatible with a
+    correct one by accident shares almost none -- so the measure separates a handful of inliers from accidental degrees that the
+    first-order degree of correspondence_compatibility cannot tell apart.
+
+    x, y, idx, threshold, min_length, x_rows: exactly as correspondence_compatibility.  return_adjacency: a bool.
+
+    Definition (continues rules 1-5 of correspondence_compatibility; integers only from rule 6 on):
+     6. W = ceil(n / 64).  adj (N, n, W) int64 over the PACKED positions: bit q % 64 of word q // 64 of row p, counted from the least
+        significant bit, is 1 iff p < P, q < P, p != q and p, q are compatible by rule 2; every other bit is 0.
+     7. common(p, q) = sum_w popcount(adj[p, w] & adj[q, w]);  S(p, q) = common(p, q) if bit (p, q) is set, else 0 (the matrix M o M^2);
+        degree2_p = sum_q S(p, q), an int64: twice the triangles through p.
+     8. rank2_p = the number of live q with degree2_q > degree2_p, or degree2_q == degree2_p and q < p, compared as integers.
+        score2_p = T(degree2_p) / T(max_q degree2_q), both operations correctly rounded; 0 where the maximum is 0.
+
+    Returns (score2, degree2, degree): (N, n) or (n,) in the original row order -- score2 in x's dtype, degree2 int64, degree int32 (rule 3)
+    -- 0 on rows that are not live; with return_adjacency=True also adj (N, n, W) / (n, W) int64, in packed order.  No gradient.
+
+    Memory: N n W 8 bytes of adjacency bits, O(n^2 / 8) per cloud -- 32 MB per cloud at n = 16384; shapes with n > 2^20 or 2^40 words and
+    more are a ValueError.  Time: n^2 W word pairs per cloud: faster than ten first-order passes at a few thousand matches, slower from
+    about ten thousand on (README, "Second-order compatibility").  A clique of wrong matches that keep their lengths to each other by
+    accident can outrank the inliers when it is as large as their set.
+
+    Nothing is read back, the grids are sized by n, and no launch depends on device data: a call on device tensors can sit in a captured
+    graph.  The only atomics are integer additions: the same bytes on every run.
+
+    Kernels (libdicp_hip.so): dicp_select_rows packs the live pairs; dicp_compat2_bits (one first-order pass that stores its decisions as
+    bits), dicp_compat2_common (AND + popcount over the rows' words, a register tile of counts per lane), dicp_compat2_rank.
+    """
+    what = "second_order_compatibility"
+    _check_compat2(threshold, min_length, what)
+    if not isinstance(return_adjacency, bool):
+        raise ValueError("%s: return_adjacency must be True or False, got %r" % (what, return_adjacency))
+    form, on_cpu, xd, yd, idx_d, _, rows = _pair_arguments(x, y, idx, None, x_rows, what)
+    st = _compat2_stages(xd, yd, idx_d, rows, threshold, min_length)
+    outs = [st["score2"], st["degree2"], st["degree"]]
+    if return_adjacency:
+        outs.append(st["adj"])
+    return _compat_outputs(form, on_cpu, outs)
+
+
+def consensus_correspondences(x, y, idx, threshold, inlier_threshold=None, seeds=64, members=16, refine=1, weight=None, min_length=0.0, x_rows=None,
+                              return_hypothesis=False):
+    """A rigid transform from putative correspondences of which nearly all may be wrong: the hypotheses are not random triples but the
+    consensus sets around the matches of the highest second-order compatibility (SC2-PCR's seeds), scored, chosen and refined by
+    ransac_correspondences' own stages -- on the GPU, per cloud, with no read-back and no random numbers.
+
+    x, y, idx, weight, x_rows: exactly as ransac_correspondences.  threshold, min_length: the compatibility relation's, as
+    correspondence_compatibility.  inlier_threshold: None (threshold) or a finite number > 0: the inlier distance of rules 4-6 of
+    ransac_correspondences.  seeds: an int in [1, 65536].  members: an int in [3, 32].  refine: an int in [0, 8].  Anything else is a
+    ValueError before any device work.
+
+    Definition (continues rules 6-8 of second_order_compatibility):
+     9. Hypothesis h, 0 <= h < min(seeds, P), is the live pair s with rank2_s == h.  Its members are s, then the first
+        min(members - 1, #{q : S(s, q) > 0}) positions q in the order S(s, q) descending, q ascending.
+    10. Its pose is rule 3 of ransac_correspondences over the list: the 18 Kabsch sums in double from 0, the members added in list order
+        at weight 1, the same closed form, one rounding to T.  A hypothesis that does not exist (h >= P) or has fewer than three members
+        (exactly the seeds with degree2 = 0, which rank behind every other) has the identity pose and count 0, as a cloud without
+        hypotheses has in ransac_correspondences: it is never chosen over a real one.
+    11. From the poses on, rules 4-6 of ransac_correspondences with inlier_threshold: counts, best (ties to the lowest h), I_0, the
+        `refine` LO rounds, and T = align_correspondences(x, y, where(inliers, idx, -1), weight, x_rows).  A cloud with P < 3: best -1,
+        best_count 0, no inliers.
+
+    Returns (T, inliers) as ransac_correspondences; with return_hypothesis=True also best (N,) int32, best_count (N,) int32, T_best
+    (N, 4, 4) and members (N, seeds, members) int32: packed positions, -1 in the unused slots.
+
+    Gradients flow through the final fit only, to x, y and weight.  Memory and time are second_order_compatibility's, O(n^2 / 8) bytes
+    per cloud, plus seeds x degree x W words for the seed rows.  Nothing is read back, no launch depends on device data (fit for a
+    captured graph), integer atomics only: bit-reproducible.
+
+    Kernels (libdicp_hip.so): those of second_order_compatibility, dicp_compat2_seeds (a wave per hypothesis: S over the seed row's set
+    bits, the member list, the fit in double), then dicp_ransac_score / _best and dicp_pair_residuals.
+    """
+    what = "consensus_correspondences"
+    _check_compat2(threshold, min_length, what)
+    thr_in = threshold if inlier_threshold is None else inlier_threshold
+    if isinstance(seeds, bool) or not isinstance(seeds, int) or not (1 <= seeds <= H_MAX):
+        raise ValueError("%s: seeds must be an int in [1, %d], got %r" % (what, H_MAX, seeds))
+    if isinstance(thr_in, bool) or not isinstance(thr_in, (int, float)) or not (0.0 < float(thr_in) < float("inf")):
+        raise ValueError("%s: inlier_threshold must be None or a finite number > 0, got %r" % (what, inlier_threshold))
+    _check_ransac(thr_in, seeds, None, refine, return_hypothesis, what)
+    if isinstance(members, bool) or not isinstance(members, int) or not (MEMBERS_MIN <= members <= MEMBERS_MAX):
+        raise ValueError("%s: members must be an int in [%d, %d], got %r" % (what, MEMBERS_MIN, MEMBERS_MAX, members))
+    form, on_cpu, xd, yd, idx_d, w, rows = _pair_arguments(x, y, idx, weight, x_rows, what)
+    st = _consensus_stages(xd, yd, idx_d, w, rows, threshold, thr_in, seeds, members, refine, min_length)
+    inl = st["inliers"]
+    T = _align(xd, yd, torch.where(inl, idx_d, torch.full_like(idx_d, -1)), w, rows)
+    outs = [T, inl]
+    if return_hypothesis:
+        outs += [st["best"], st["best_count"], _T44(st["pose_best"]), st["members"]]
+    if on_cpu:
+        outs = [t.cpu() for t in outs]
+    if form == "single":
+        outs[0], outs[1] = outs[0][0], outs[1][0]
+    return tuple(outs)
+
+
+def _consensus_stages(xd, yd, idx_d, weight, rows, threshold, inlier_threshold, seeds, members, refine, min_length):
+    """Every stage of consensus_correspondences on _pair_arguments' tensors: _compat2_stages' dict plus _score_and_refine's outputs under
+    the names _ransac_stages uses.  Nothing is read back."""
+    st = _compat2_stages(xd, yd, idx_d, rows, threshold, min_length, seeds=seeds, members=members)
+    with torch.no_grad():
+        counts, best, best_count, pose_best, thr2, sets, accepted, round_poses, inl = _score_and_refine(
+            xd.detach(), yd.detach(), idx_d, st["idx32"], weight, rows, st["pairs"], st["P"], st["poses"], inlier_threshold, refine, real=st["real"])
+    st.update(counts=counts, best=best, best_count=best_count, pose_best=pose_best, thr2=thr2, sets=sets, accepted=accepted, round_poses=round_poses,
+              inliers=inl)
+    return st

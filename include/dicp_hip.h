@@ -1175,6 +1175,31 @@ int dicp_compat_scores(int dtype, const void* pairs, const int32_t* P, int N, in
                        void* wmax, void* score, int32_t* degree, void* stream);
 int dicp_compat_rank(int dtype, const void* score, const int32_t* P, int N, int n, int32_t* rank, void* stream);
 
+/* Second-order compatibility and seeded consensus (dicp_amd/match.py: second_order_compatibility / prune_correspondences(order=2) /
+ * consensus_correspondences; csrc/compat2.hip, the rules: csrc/dicp_compat2.h).  pairs, P, threshold and min_length as above; 1 <= n <= 2^20
+ * and N n W < 2^40 with W = ceil(n / 64) (DICP_ERR_SHAPE).  Everything past the relation is integer arithmetic; the only atomics are
+ * integer additions: every output is bit-reproducible.  Nothing is read back.  Additive to ABI 11.
+ * dicp_compat2_bits: adj (N,n,W) int64: bit q % 64 (from the least significant) of word q / 64 of row p is 1 iff p < P, q < P, p != q and
+ *   the two are compatible; every other bit, rows at or past P included, is 0.  degree (N,n) int32 = the popcount of the row;
+ *   degree2 (N,n) int64 is zeroed for dicp_compat2_common.
+ * dicp_compat2_common: degree2[p] += sum_q S(p, q), S(p, q) = sum_w popcount(adj[p,w] & adj[q,w]) where bit (p, q) is set and 0 elsewhere:
+ *   a workgroup takes `rows` rows p x `chunk` rows q and stages `words` words of both per step (dicp_compat2_geometry).
+ * dicp_compat2_rank: rank2 (N,n) int32 = the number of q below P with degree2_q > degree2_p, or equal and q < p (INT32_MAX at and past P);
+ *   score2 (N,n) T = T(degree2_p) / T(max_q degree2_q), 0 where the maximum is 0 and at and past P.  seeds in [0, 65536]: with seeds > 0,
+ *   seedpos (N,seeds) int32 receives the row of every rank below min(seeds, P) (the other entries are not written); seeds = 0 takes NULL.
+ * dicp_compat2_seeds: hypothesis h < min(seeds, P) is the row s = seedpos[h]; member_list (N,seeds,members) int32 = s, then the first
+ *   min(members - 1, #{q : S(s,q) > 0}) rows q in the order (S(s,q) descending, q ascending), -1 in the unused slots and everywhere for
+ *   h >= P; poses (N,seeds,12) T = the closed form of dicp_ransac_hypotheses over the list (the 18 sums in double in member order, one
+ *   rounding to T), the identity for fewer than three members.  1 <= seeds <= 65536, 3 <= members <= 32 (DICP_ERR_SHAPE). */
+void dicp_compat2_geometry(int* rows, int* tile, int* words, int* chunk);
+int dicp_compat2_bits(int dtype, const void* pairs, const int32_t* P, int N, int n, double threshold, double min_length, int64_t* adj, int32_t* degree,
+                      int64_t* degree2, void* stream);
+int dicp_compat2_common(const int64_t* adj, const int32_t* P, int N, int n, int64_t* degree2, void* stream);
+int dicp_compat2_rank(int dtype, const int64_t* degree2, const int32_t* P, int N, int n, int seeds, int32_t* rank2, void* score2, int32_t* seedpos,
+                      void* stream);
+int dicp_compat2_seeds(int dtype, const void* pairs, const int32_t* P, const int64_t* adj, const int32_t* seedpos, int N, int n, int seeds, int members,
+                       int32_t* member_list, void* poses, void* stream);
+
 /* FPFH descriptors, 33 channels (dicp_amd/fpfh.py: fpfh_features / compute_fpfh; csrc/fpfh.hip, the rules: csrc/dicp_fpfh.h).  points
  * (N,m,c) T with c >= 3 (columns 0:3 are read), normals (N,m,3) T, idx (N,m,k) int64 (idx64 = 1) or int32 (idx64 = 0; anything else:
  * DICP_ERR_ENUM), a search of every cloud against ITSELF with 1 <= k <= 32; rows: optional (N) row counts.  radius: 0 for none, otherwise
