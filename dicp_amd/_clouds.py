@@ -1,4 +1,4 @@
-"""The cloud arguments of the point-cloud operators (normals, voxel, knn, fps, ball, group, match, fpfh): one cloud, a padded batch with row counts, or a list.
+"""The cloud arguments of the point-cloud operators (normals, voxel, knn, fps, ball, group, match, fpfh, iss): one cloud, a padded batch with row counts, or a list.
 
 check / check_pair / check_slots / check_table validate on the host (no device is touched), place moves a checked batch to the compute device, restore
 cuts the library's (N, ...) results back to the caller's form and device.  What differs between the operators is an argument at their call

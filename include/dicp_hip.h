@@ -1222,6 +1222,31 @@ int dicp_fpfh_spfh(int dtype, const void* points, int c, const void* normals, co
 int dicp_fpfh_combine(int dtype, const void* points, int c, const void* idx, int idx64, const int32_t* rows, int N, int m, int k, double radius,
                       const void* workspace, size_t workspace_bytes, void* out, void* stream);
 
+/* ISS keypoints (dicp_amd/iss.py: iss_saliency / iss_keypoints / compute_iss_keypoints; csrc/iss.hip, the rules: csrc/dicp_iss.h).
+ * points (N,m,c) T with c >= 3 (columns 0:3 are read), idx (N,m,k) int64 (idx64 = 1) or int32 (idx64 = 0; anything else: DICP_ERR_ENUM),
+ * a search of every cloud against ITSELF with 1 <= k <= 32; rows: optional (N) row counts.  radius: 0 for none, otherwise finite and > 0;
+ * radius2 = radius radius in double.  gamma21, gamma32 in (0, 1], min_neighbors >= 1 (DICP_ERR_SHAPE).  Everything is computed in
+ * double from the exactly converted inputs with + - * / sqrt only, no fma; nothing is read back; no float atomics: every output is
+ * bit-reproducible.
+ *   Row i is OK when its coordinates are finite.  The MEMBERS of row i < rows[b] are the row itself, then in slot order the slots naming
+ *   a row j with 0 <= j < rows[b] (so nothing is read out of range whatever idx holds), j != i, row j OK and r2 = (dx dx + dy dy) + dz dz
+ *   <= radius2 for d = p_j - p_i if there is a radius; count is their number.
+ * dicp_iss_saliency: over the members, the covariance of q = p_j - p_i about its mean (sums in member order from +0, divided by count),
+ *   its eigenvalues l0 <= l1 <= l2 by ISS_SWEEPS = 6 cyclic Jacobi sweeps exactly as csrc/dicp_iss.h states them, and sal = l0 when
+ *   count >= min_neighbors, l1 < gamma21 l2 and 0 < l0 < gamma32 l1, else 0.  The double saliency of every row goes to `workspace`; the
+ *   optional outputs saliency_out (N,m) T, eigenvalues_out (N,m,3) T (each rounded once) and count_out (N,m) may be NULL.  Rows that are
+ *   not OK or at or past rows[b] get 0 everywhere.
+ * dicp_iss_maxima: mask_out (N,m) bytes, 1 for a keypoint, from the workspace that dicp_iss_saliency left for the SAME points and rows
+ *   (idx, k and radius may be others): sal_i > 0, the member count for THIS idx and radius >= min_neighbors, and no member j has
+ *   sal_j > sal_i, or sal_j == sal_i and j < i.
+ *   workspace: dicp_iss_workspace_bytes(N, m) bytes (0 for bad arguments or N m >= 2^31), 256-byte aligned. */
+size_t dicp_iss_workspace_bytes(int N, int m);
+int dicp_iss_saliency(int dtype, const void* points, int c, const void* idx, int idx64, const int32_t* rows, int N, int m, int k, double radius,
+                      double gamma21, double gamma32, int min_neighbors, void* workspace, size_t workspace_bytes, void* saliency_out,
+                      void* eigenvalues_out, int32_t* count_out, void* stream);
+int dicp_iss_maxima(int dtype, const void* points, int c, const void* idx, int idx64, const int32_t* rows, int N, int m, int k, double radius,
+                    int min_neighbors, const void* workspace, size_t workspace_bytes, uint8_t* mask_out, void* stream);
+
 /* Soft descriptor matches (dicp_amd/match.py: soft_match_features; csrc/softmatch.hip, the rules: csrc/dicp_softmatch.h).  x (N,n,D) T,
  * y (N,m,D) T, values (N,m,C) T, 1 <= D <= 256, 1 <= C <= 8, tau finite and > 0 with (T)(-2.0 / tau) finite and non-zero (DICP_ERR_SHAPE);
  * x_rows / y_rows: optional (N) row counts as tgt_rows.  The score s_ij and the candidates of query i are dicp_knn_features', bit for bit.
