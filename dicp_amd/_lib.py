@@ -11,8 +11,8 @@ import threading
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 LIB_PATH = os.environ.get("DICP_HIP_LIB") or os.path.join(_HERE, "libdicp_hip.so")   # env override: A/B builds
-SOURCES = [os.path.join(_HERE, "csrc", f) for f in ("dicp_kernels.hip", "knn_f16.hip", "dicp_call.hip", "normals.hip", "voxel.hip", "knn_points.hip", "fps.hip", "ball_query.hip", "knn_grid.hip", "group.hip", "inverse.hip", "knn_det.hip", "normals_det.hip", "filter.hip", "match.hip", "ransac.hip", "compat.hip", "compat2.hip", "fpfh.hip", "softmatch.hip", "iss.hip")]
-HEADERS = ([os.path.join(_HERE, "csrc", f) for f in ("dicp_math.h", "dicp_common.h", "dicp_internal.h", "dicp_fill.h", "dicp_normals.h", "dicp_voxel.h", "dicp_topk.h", "dicp_fps.h", "dicp_ball.h", "dicp_gridknn.h", "kernels_grid.h", "kernels_grid_plan.h", "dicp_group.h", "dicp_group_launch.h", "dicp_inverse.h", "dicp_knn_det.h", "kernels_normals.h", "dicp_normals_det.h", "dicp_filter.h", "dicp_match.h", "dicp_ransac.h", "dicp_compat.h", "dicp_compat2.h", "dicp_fpfh.h", "dicp_softmatch.h", "dicp_iss.h")]
+SOURCES = [os.path.join(_HERE, "csrc", f) for f in ("dicp_kernels.hip", "knn_f16.hip", "dicp_call.hip", "normals.hip", "voxel.hip", "knn_points.hip", "fps.hip", "ball_query.hip", "knn_grid.hip", "group.hip", "inverse.hip", "knn_det.hip", "normals_det.hip", "filter.hip", "match.hip", "ransac.hip", "compat.hip", "compat2.hip", "fpfh.hip", "softmatch.hip", "iss.hip", "gnc.hip")]
+HEADERS = ([os.path.join(_HERE, "csrc", f) for f in ("dicp_math.h", "dicp_common.h", "dicp_internal.h", "dicp_fill.h", "dicp_normals.h", "dicp_voxel.h", "dicp_topk.h", "dicp_fps.h", "dicp_ball.h", "dicp_gridknn.h", "kernels_grid.h", "kernels_grid_plan.h", "dicp_group.h", "dicp_group_launch.h", "dicp_inverse.h", "dicp_knn_det.h", "kernels_normals.h", "dicp_normals_det.h", "dicp_filter.h", "dicp_match.h", "dicp_ransac.h", "dicp_compat.h", "dicp_compat2.h", "dicp_fpfh.h", "dicp_softmatch.h", "dicp_iss.h", "dicp_gnc.h")]
            + [os.path.join(_HERE, "csrc", "kernels_%s.h" % f) for f in ("setup", "search", "setup_sort", "rows", "accumulate", "backward", "soft_svd", "host")]
            + [os.path.join(_ROOT, "include", "dicp_hip.h")])
 
@@ -23,6 +23,7 @@ KNN_AUTO, KNN_VALU, KNN_MFMA, KNN_SWEEP, KNN_GUMBEL = 0, 1, 2, 3, 4
 FPS_AUTO, FPS_RESIDENT, FPS_STREAMED = 0, 1, 2
 POOL_SUM, POOL_MEAN, POOL_MAX = 0, 1, 2
 MATCH_AUTO, MATCH_VALU, MATCH_MFMA = 0, 1, 2
+GNC_TLS, GNC_GM = 0, 1
 NACC_PAD, NBWD_PAD, KAB_SAVE = 32, 16, 40
 PAIR_SHARDS = 64      # DICP_PAIR_SHARDS
 ABI_VERSION = 11
@@ -295,6 +296,7 @@ _SIGNATURES = {
     "dicp_ransac_score": ([i32, vp, vp, vp, i32, i32, i32, f64, vp, vp], ctypes.c_int),
     "dicp_ransac_best": ([i32, vp, vp, vp, i32, i32, vp, vp, vp, vp], ctypes.c_int),
     "dicp_pair_residuals": ([i32, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp], ctypes.c_int),
+    "dicp_gnc_fit": ([i32, vp, vp, vp, i32, i32, i32, f64, f64, i32, vp, vp, vp, vp, vp, vp, vp], ctypes.c_int),
     "dicp_compat_geometry": ([ctypes.POINTER(i32), ctypes.POINTER(i32)], None),
     "dicp_compat_scores": ([i32, vp, vp, i32, i32, i32, f64, f64, vp, vp, vp, vp, vp], ctypes.c_int),
     "dicp_compat_rank": ([i32, vp, vp, i32, i32, vp, vp], ctypes.c_int),

@@ -28,6 +28,10 @@ separates them in one pass, and its best matches seed the hypotheses instead of 
     score2, degree2, degree = second_order_compatibility(x, y, idx, threshold=0.05)
     idx_kept, score2 = prune_correspondences(x, y, idx, threshold=0.05, keep=256, order=2)
     T0, inliers = consensus_correspondences(x, y, idx, threshold=0.05, seeds=64, members=16)
+
+Without hypotheses at all, for inlier ratios of about 30 % and up: graduated non-convexity, one launch with a workgroup per cloud
+
+    T0, weights = gnc_correspondences(x, y, idx, threshold=0.05, loss="tls")        # or loss="gm"; dicp_gnc_fit
 """
 import torch
 
@@ -595,6 +599,122 @@ def correspondence_residuals(x, y, idx, T, x_rows=None):
     if on_cpu:
         d2 = d2.cpu()
     return d2[0] if form == "single" else d2
+
+
+GNC_ITER_MAX = 256      # GNC_ITER_MAX (csrc/dicp_gnc.h)
+GNC_TRACE = 32          # GNC_TRACE: doubles of a trace record (mu, the band count, the 18 sums, the pose)
+GNC_GROWTH_MAX = 16.0
+GNC_LOSSES = {"tls": _lib.GNC_TLS, "gm": _lib.GNC_GM}
+
+
+def _check_gnc(threshold, loss, growth, iterations, return_info, what):
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float)) or not (0.0 < float(threshold) < float("inf")) \
+            or not (0.0 < float(threshold) * float(threshold) < float("inf")):
+        raise ValueError("%s: threshold must be a finite number > 0 (with a finite square > 0), got %r" % (what, threshold))
+    if not isinstance(loss, str) or loss not in GNC_LOSSES:
+        raise ValueError('%s: loss must be "tls" or "gm", got %r' % (what, loss))
+    if isinstance(growth, bool) or not isinstance(growth, (int, float)) or not (1.0 < float(growth) <= GNC_GROWTH_MAX):
+        raise ValueError("%s: growth must be a finite number with 1 < growth <= %g, got %r" % (what, GNC_GROWTH_MAX, growth))
+    if isinstance(iterations, bool) or not isinstance(iterations, int) or not (1 <= iterations <= GNC_ITER_MAX):
+        raise ValueError("%s: iterations must be an int in [1, %d], got %r" % (what, GNC_ITER_MAX, iterations))
+    if not isinstance(return_info, bool):
+        raise ValueError("%s: return_info must be True or False, got %r" % (what, return_info))
+
+
+def _gnc_stages(xd, yd, idx_d, weight, rows, threshold, loss, growth, iterations, trace=False):
+    """The kernel side of gnc_correspondences on _pair_arguments' tensors (under torch.no_grad, on detached points), as a dict: live
+    (N, n) bool, pairs (N, n, 6), u (N, n) or None and P (N,) int32 (the packed pairs and their user weights), weights_packed (N, n),
+    weights (N, n) in the original row order, rounds / status (N,) int32, mu (N,) float64, pose_last (N, 12), and with trace=True
+    trace (N, iterations + 1, 32) float64, zero past a cloud's last record.  One dicp_gnc_fit launch; nothing is read back."""
+    from .filter import _Select
+    N, n, _ = xd.shape
+    m, dt, dev = yd.shape[1], xd.dtype, xd.device
+    with torch.no_grad():
+        x0, y0 = xd.detach(), yd.detach()
+        if weight is None:
+            _, live, pairs, P, _ = _live_pairs(x0, y0, idx_d, rows)
+            u = None
+        else:                                                   # rule 1 with the weight's own condition; the weights ride along as a seventh column
+            w0 = weight.detach()
+            idx32 = _idx32(idx_d, m)
+            yg = torch.gather(y0, 1, idx32.clamp(min=0, max=m - 1).long()[..., None].expand(N, n, 3))
+            live = (idx32 >= 0) & torch.isfinite(x0).all(dim=-1) & torch.isfinite(yg).all(dim=-1) & torch.isfinite(w0) & (w0 > 0)
+            if rows is not None:
+                live &= torch.arange(n, device=dev)[None, :] < rows[:, None]
+            packed, P, _ = _Select.apply(torch.cat((x0, yg, w0[..., None]), dim=-1).contiguous(), live.contiguous(), None, False)
+            pairs, u = packed[..., :6].contiguous(), packed[..., 6].contiguous()
+        wp = torch.empty((N, n), dtype=dt, device=dev)
+        rounds = torch.empty((N,), dtype=torch.int32, device=dev)
+        status = torch.empty((N,), dtype=torch.int32, device=dev)
+        mu = torch.empty((N,), dtype=torch.float64, device=dev)
+        pose = torch.empty((N, 12), dtype=dt, device=dev)
+        tr = torch.zeros((N, int(iterations) + 1, GNC_TRACE), dtype=torch.float64, device=dev) if trace else None
+        _lib.call("dicp_gnc_fit", dev, _DT[dt], _p(pairs), _p(P), _p(u), N, n, GNC_LOSSES[loss], float(threshold), float(growth), int(iterations),
+                  _p(wp), _p(rounds), _p(status), _p(mu), _p(pose), _p(tr))
+        pos = (torch.cumsum(live, dim=1) - 1).clamp(min=0)      # the packed position of every live row
+        weights = torch.where(live, torch.gather(wp, 1, pos), torch.zeros((), dtype=dt, device=dev))
+    return dict(live=live, pairs=pairs, u=u, P=P, weights_packed=wp, weights=weights, rounds=rounds, status=status, mu=mu, pose_last=pose, trace=tr)
+
+
+def gnc_correspondences(x, y, idx, threshold, loss="tls", growth=1.4, iterations=128, weight=None, x_rows=None, return_info=False):
+    """A rigid transform from putative correspondences of which many are wrong, by graduated non-convexity: iteratively re-weighted
+    closed-form alignment under a robust cost that starts convex and is sharpened round by round -- truncated least squares (Yang et
+    al. 2020, the rotation stage of TEASER++) or Geman-McClure (Fast Global Registration).  No seed, no hypothesis count; ONE kernel
+    launch, a workgroup per cloud that runs every round and takes the stopping decision on the device.
+
+    x, y, idx, weight, x_rows: exactly as align_correspondences (single clouds or padded batches, float32 or float64, columns 0:3, idx
+        int32 or int64 with negative = no match; CPU tensors are computed on the GPU and returned on the CPU).
+    threshold: a finite number > 0, the inlier distance (not squared).  loss: "tls" or "gm".  growth: a finite number g, 1 < g <= 16.
+    iterations: an int in [1, 256].  return_info: a bool.  Anything else is a ValueError before any device work.
+
+    Definition (hardware-independent; everything after the packing in double on the exactly converted inputs, + - * / sqrt and
+    comparisons only, no fma; c2 = threshold threshold):
+     1. Live pairs: rule 1 of ransac_correspondences, and where weight is given weight_i finite and > 0.  The live pairs in ascending row
+        order, P per cloud; u_p the user weight (1 without one).
+     2. The fit F(w): the 18 Kabsch sums from 0 with pair p at omega_p = u_p w_p (a pair with omega_p = 0 contributes nothing), then
+        the closed form of align_correspondences (proper rotation, rank-deficient completion).  The order of the sums is fixed: slot
+        s = p mod 1024 adds its pairs in ascending p, then the slots are added pairwise, v_i + v_(i+off) for off = 1, 2, 4, ..., 512 -- a
+        function of P alone.  The pose stays in double between rounds.
+     3. The residual d_p = |C x_p + r - y_p|^2: q_a = ((C_a0 x_0 + C_a1 x_1) + C_a2 x_2) + r_a, e_a = q_a - y_a, d = (e_0^2 + e_1^2) + e_2^2;
+        a d that is not finite counts as +inf and gets weight 0.
+     4. Round 0: w = 1, pose = F(w), then d; dmax = the largest finite d (0 if none).  A cloud with P < 3 runs nothing: weights 0,
+        rounds 0, status 3, T = align_correspondences' result for no pairs, T_last the identity.
+     5. loss="tls": if 2 dmax <= c2 stop (all inliers, status 0, weights 1); else mu = c2 / (2 dmax - c2).  A round: lo = (mu / (mu + 1)) c2,
+        hi = ((mu + 1) / mu) c2;  w_p = 1 for d_p <= lo, 0 for d_p >= hi, and in the band sqrt(((c2 mu) (mu + 1)) / d_p) - mu (clamped into
+        [0, 1]: only a last bit);  pose = F(w), new d.  Stop after a round whose band was empty, status 0; otherwise mu = mu g.
+     6. loss="gm": mu = max(1, 2 dmax / c2).  A round: t = mu c2, w_p = (t / (d_p + t))^2;  pose = F(w), new d.  Stop after the round
+        run at mu = 1, status 0; otherwise mu = max(1, mu / g).
+     7. Guard: a round that would leave fewer than three pairs with omega_p > 0 is not applied; the previous pose and weights stand and
+        the loop stops, status 2.
+     8. Cap: after `iterations` applied rounds the loop stops, status 1 (a round that meets its own stopping rule there has status 0).
+
+    Returns (T, weights): weights (N, n) / (n,) in the points' dtype and the original row order -- the final w rounded once, exactly 0 on
+    rows that are not live, never requiring grad -- and T (N, 4, 4) / (4, 4) = align_correspondences(x, y, where(weights > 0, idx, -1),
+    weight weights, x_rows).  With return_info=True also rounds (N,) int32 (the applied rounds), status (N,) int32, mu (N,) float64 (the
+    mu of the last applied round, 0 if none) and T_last (N, 4, 4), the kernel's own last pose rounded once.
+
+    Gradients flow through the final fit only, to x, y and weight (align_correspondences' backward); the GNC weights are constants.
+    Nothing is read back and no launch depends on device data: a call on device tensors can sit in a captured graph.  No float atomics
+    in the forward: the result is bit-reproducible.
+
+    For inlier ratios of about 30 % and up.  Below that put prune_correspondences(order=2) in front (README).
+
+    Kernels (libdicp_hip.so): dicp_select_rows packs the live pairs, dicp_gnc_fit (csrc/gnc.hip, the rules: csrc/dicp_gnc.h).
+    """
+    what = "gnc_correspondences"
+    _check_gnc(threshold, loss, growth, iterations, return_info, what)
+    form, on_cpu, xd, yd, idx_d, w, rows = _pair_arguments(x, y, idx, weight, x_rows, what)
+    st = _gnc_stages(xd, yd, idx_d, w, rows, threshold, loss, growth, iterations)
+    wg = st["weights"]
+    T = _align(xd, yd, torch.where(wg > 0, idx_d, torch.full_like(idx_d, -1)), wg if w is None else w * wg, rows)
+    outs = [T, wg]
+    if return_info:
+        outs += [st["rounds"], st["status"], st["mu"], _T44(st["pose_last"])]
+    if on_cpu:
+        outs = [t.cpu() for t in outs]
+    if form == "single":
+        outs[0], outs[1] = outs[0][0], outs[1][0]
+    return tuple(outs)
 
 
 ITER_MAX = 64           # COMPAT_ITER_MAX (csrc/dicp_compat.h)

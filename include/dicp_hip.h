@@ -1157,6 +1157,20 @@ int dicp_ransac_best(int dtype, const int32_t* counts, const void* poses, const 
 int dicp_pair_residuals(int dtype, const void* x, const void* y, const int32_t* idx, const int32_t* x_rows, const void* pose, int N, int n, int m,
                         void* d2, void* stream);
 
+/* Graduated non-convexity over explicit correspondences (dicp_amd/match.py: gnc_correspondences; csrc/gnc.hip, the rules, the order of the
+ * sums and the stopping rules: csrc/dicp_gnc.h).  pairs (N,n,6) T and P (N) int32 as for RANSAC above; u: optional (N,n) T, the user
+ * weight of every PACKED pair (NULL: 1).  loss: 0 = truncated least squares, 1 = Geman-McClure (anything else: DICP_ERR_ENUM).  threshold
+ * finite with 0 < threshold threshold < inf, 1 < growth <= 16, 1 <= iterations <= 256 (DICP_ERR_SHAPE).  ONE launch, one workgroup per
+ * cloud; everything in double with + - * / sqrt only, no fma; no float atomics, nothing read back: every output is bit-reproducible.
+ *   weights_packed (N,n) T: the weight w of the last applied round rounded once (1 when no round was applied), 0 at and past P and
+ *   everywhere for P < 3.  rounds (N) int32: the applied rounds.  status (N) int32: 0 = stopped by its rule, 1 = `iterations` rounds,
+ *   2 = a round would have left fewer than three pairs with u w > 0 (not applied), 3 = P < 3.  mu (N) double: of the last applied round,
+ *   0 if none.  pose_last (N,12) T: the last pose (C row-major, then r), rounded once; the identity for P < 3.  trace: optional
+ *   (N, iterations + 1, 32) double, record 0 for round 0 and record k for applied round k: mu, the band count, the 18 sums, the pose in
+ *   double; the other records are not written.  Additive to ABI 11. */
+int dicp_gnc_fit(int dtype, const void* pairs, const int32_t* P, const void* u, int N, int n, int loss, double threshold, double growth, int iterations,
+                 void* weights_packed, int32_t* rounds, int32_t* status, double* mu, void* pose_last, double* trace, void* stream);
+
 /* Spatial compatibility of correspondences (dicp_amd/match.py: correspondence_compatibility / prune_correspondences; csrc/compat.hip, the
  * rules: csrc/dicp_compat.h).  pairs (N,n,6) T and P (N) int32 as for RANSAC above.  thr = T(threshold), L = T(min_length); threshold finite
  * and > 0, min_length finite and >= 0, 0 <= iterations <= 64 (DICP_ERR_SHAPE).  fma, sqrt and / are the correctly rounded ones of T.
