@@ -81,19 +81,20 @@ def check(t, rows, what, name="points", rows_name="rows", empty_ok=False, flat_r
     return form, batch, rows, lens
 
 
-def check_pair(x, y, x_rows, y_rows, what):
-    """check on both arguments of a two-cloud operator (either side may be empty), and that they go together -> (check(x), check(y))"""
-    cx = check(x, x_rows, what, "x", "x_rows", empty_ok=True)
-    cy = check(y, y_rows, what, "y", "y_rows", empty_ok=True)
+def check_pair(x, y, x_rows, y_rows, what, nx="x", ny="y", min_cols=3):
+    """check on both arguments of a two-cloud operator (either side may be empty), and that they go together -> (check(x), check(y));
+    nx, ny: the arguments' names in the messages"""
+    cx = check(x, x_rows, what, nx, "x_rows", empty_ok=True, min_cols=min_cols)
+    cy = check(y, y_rows, what, ny, "y_rows", empty_ok=True, min_cols=min_cols)
     bx, by = cx[1], cy[1]
     if cx[0] != cy[0]:
-        _err(what, "x and y must have the same form (single clouds, padded batches or lists), got %s and %s" % (cx[0], cy[0]))
+        _err(what, "%s and %s must have the same form (single clouds, padded batches or lists), got %s and %s" % (nx, ny, cx[0], cy[0]))
     if bx.dtype != by.dtype:
-        _err(what, "x and y must have one dtype, got %s and %s" % (bx.dtype, by.dtype))
+        _err(what, "%s and %s must have one dtype, got %s and %s" % (nx, ny, bx.dtype, by.dtype))
     if bx.device != by.device:
-        _err(what, "x and y must be on one device, got %s and %s" % (bx.device, by.device))
+        _err(what, "%s and %s must be on one device, got %s and %s" % (nx, ny, bx.device, by.device))
     if bx.shape[0] != by.shape[0]:
-        _err(what, "x and y must hold the same number of clouds, got %d and %d" % (bx.shape[0], by.shape[0]))
+        _err(what, "%s and %s must hold the same number of clouds, got %d and %d" % (nx, ny, bx.shape[0], by.shape[0]))
     return cx, cy
 
 
@@ -241,17 +242,7 @@ def pair(x, y, x_rows, y_rows, what):
 
 def pair_features(x, y, x_rows, y_rows, what, d_max):
     """pair for two descriptor tables (match.py): every column takes part (1 <= D <= d_max, the same D on both sides) -> pair's tuple"""
-    cx = check(x, x_rows, what, "fx", "x_rows", empty_ok=True, min_cols=1)
-    cy = check(y, y_rows, what, "fy", "y_rows", empty_ok=True, min_cols=1)
-    (form, bx, rx, lx), (_, by, ry, _) = cx, cy
-    if cx[0] != cy[0]:
-        _err(what, "fx and fy must have the same form (single clouds, padded batches or lists), got %s and %s" % (cx[0], cy[0]))
-    if bx.dtype != by.dtype:
-        _err(what, "fx and fy must have one dtype, got %s and %s" % (bx.dtype, by.dtype))
-    if bx.device != by.device:
-        _err(what, "fx and fy must be on one device, got %s and %s" % (bx.device, by.device))
-    if bx.shape[0] != by.shape[0]:
-        _err(what, "fx and fy must hold the same number of clouds, got %d and %d" % (bx.shape[0], by.shape[0]))
+    (form, bx, rx, lx), (_, by, ry, _) = check_pair(x, y, x_rows, y_rows, what, "fx", "fy", min_cols=1)
     if bx.shape[2] != by.shape[2] or bx.shape[2] > d_max:
         _err(what, "fx and fy need the same number of channels D in [1, %d], got %d and %d" % (d_max, bx.shape[2], by.shape[2]))
     on_cpu, bx_d, rx_d = place(bx, rx)

@@ -19,6 +19,7 @@ sys.path.insert(0, os.path.join(ROOT, "scripts"))
 from compat_bench import WAVE_ISSUE_PER_S, make, timed  # noqa: E402
 from dicp_amd import _lib  # noqa: E402
 from dicp_amd import match as M  # noqa: E402
+from dicp_amd._pairs import _live_pairs  # noqa: E402
 from dicp_amd._ops import _DT, _p  # noqa: E402
 
 N, THR = 32, 0.02
@@ -30,7 +31,8 @@ def stage_times(x, y, idx, lines):
     n, dt, dev = x.shape[1], x.dtype, x.device
     code = _DT[dt]
     W = (n + 63) // 64
-    _, _, pairs, P, _ = M._live_pairs(x, y, idx, None)
+    pk = _live_pairs(x, y, idx, None)
+    pairs, P = pk.pairs, pk.P
     adj = torch.empty((N, n, W), dtype=torch.int64, device=dev)
     dp = torch.empty((N, n), dtype=torch.int32, device=dev)
     d2 = torch.empty((N, n), dtype=torch.int64, device=dev)

@@ -17,6 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from dicp_amd import _lib  # noqa: E402
 from dicp_amd import match as M  # noqa: E402
+from dicp_amd._pairs import _live_pairs  # noqa: E402
 from dicp_amd._ops import _DT, _p  # noqa: E402
 
 REPS = 5
@@ -90,12 +91,13 @@ def main():
             name = str(dtype).split(".")[1]
             lines.append("%s n %d" % (name, n))
             print(lines[-1], flush=True)
-            _, live, pairs, P, _ = M._live_pairs(x, y, idx, None)
+            pk = _live_pairs(x, y, idx, None)
+            live, pairs, P = pk.live, pk.pairs, pk.P
             w = torch.empty((2, N, n), dtype=dtype, device=dev)
             sp = torch.empty((N, n), dtype=dtype, device=dev)
             dp = torch.empty((N, n), dtype=torch.int32, device=dev)
             rank = torch.empty((N, n), dtype=torch.int32, device=dev)
-            t_pack = timed(lambda: M._live_pairs(x, y, idx, None), lines, "pack (gather, mask, select_rows)")
+            t_pack = timed(lambda: _live_pairs(x, y, idx, None), lines, "pack (gather, mask, select_rows)")
 
             def scores(it):
                 wmax = torch.zeros((max(it, 1), N), dtype=torch.int32 if dtype == torch.float32 else torch.int64, device=dev)

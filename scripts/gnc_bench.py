@@ -17,7 +17,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from dicp_amd import _lib  # noqa: E402
-from dicp_amd import match as M  # noqa: E402
+from dicp_amd import register as M  # noqa: E402
 from dicp_amd._ops import _DT, _p  # noqa: E402
 
 REPS = 5
@@ -140,7 +140,8 @@ def main():
                 st = {}
 
                 def pack():
-                    _, _, st["pairs"], st["P"], _ = M._live_pairs(x, y, idx, None)
+                    pk = M._live_pairs(x, y, idx, None)
+                    st["pairs"], st["P"] = pk.pairs, pk.P
                 t_pack = timed(pack, lines, "pack (gather, mask, select_rows)")
                 ransac = {}
                 for H in (1024, 4096):
@@ -173,7 +174,8 @@ def main():
     print(lines[-1], flush=True)
     x, y, idx = make(256, 64, 0.5, torch.float32)
     st = {}
-    _, _, st["pairs"], st["P"], _ = M._live_pairs(x, y, idx, None)
+    pk = M._live_pairs(x, y, idx, None)
+    st["pairs"], st["P"] = pk.pairs, pk.P
     for loss in ("tls", "gm"):
         fn, rounds = launch_only(st, 256, 64, torch.float32, loss, thr)
         t = timed(fn, lines, "dicp_gnc_fit %s" % loss)

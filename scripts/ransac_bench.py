@@ -15,7 +15,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from dicp_amd import _lib  # noqa: E402
-from dicp_amd import match as M  # noqa: E402
+from dicp_amd import register as M  # noqa: E402
 from dicp_amd._ops import _DT, _p  # noqa: E402
 from dicp_amd.filter import _Select  # noqa: E402
 

@@ -1,4 +1,4 @@
-"""CPU checks of second_order_compatibility / prune_correspondences(order=2) / consensus_correspondences (dicp_amd/match.py) that need no
+"""CPU checks of second_order_compatibility / prune_correspondences(order=2) / consensus_correspondences (dicp_amd/compat.py, register.py) that need no
 GPU.
 
 1  the g++ build of csrc/dicp_compat2.h (tests/hostcheck/compat2_check.cpp: the lines the kernels run) against the numpy restatement

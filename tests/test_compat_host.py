@@ -1,4 +1,4 @@
-"""CPU checks of correspondence_compatibility / prune_correspondences (dicp_amd/match.py) that need no GPU.
+"""CPU checks of correspondence_compatibility / prune_correspondences (dicp_amd/compat.py) that need no GPU.
 
 The rules of ``dicp_amd/csrc/dicp_compat.h`` -- the lines the HIP kernels run -- are compiled with g++ through
 tests/hostcheck/compat_check.cpp, run in a serial loop and held to the numpy restatement tests/compat_ref.py bit for bit in both dtypes:

@@ -1,4 +1,4 @@
-"""CPU checks of gnc_correspondences (dicp_amd/match.py) that need no GPU.
+"""CPU checks of gnc_correspondences (dicp_amd/register.py) that need no GPU.
 
 The rules of ``dicp_amd/csrc/dicp_gnc.h`` -- the lines the HIP kernel runs -- are compiled with g++ through
 tests/hostcheck/gnc_check.cpp, run in a serial loop and held to the numpy restatement tests/gnc_ref.py: given each round's pose from the

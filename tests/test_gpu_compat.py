@@ -1,4 +1,4 @@
-"""correspondence_compatibility / prune_correspondences on the MI355X (dicp_amd/match.py; csrc/compat.hip), against the numpy restatement
+"""correspondence_compatibility / prune_correspondences on the MI355X (dicp_amd/compat.py; csrc/compat.hip), against the numpy restatement
 tests/compat_ref.py.
 
 1  score, degree and idx_kept bit for bit in float32 and float64: P at and around every edge of the kernel's block (R rows) and tile (S rows)

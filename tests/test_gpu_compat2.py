@@ -1,4 +1,4 @@
-"""second_order_compatibility / prune_correspondences(order=2) / consensus_correspondences on the MI355X (dicp_amd/match.py;
+"""second_order_compatibility / prune_correspondences(order=2) / consensus_correspondences on the MI355X (dicp_amd/compat.py, register.py;
 csrc/compat2.hip), against the numpy restatement tests/compat2_ref.py.
 
 1  every stage at the edges of the kernels' tiles -- P in {0, 1, 2, 3, 63, 64, 65, 127, 128, 129, 255, 256, 257, 511, 512, 513, 1025} with

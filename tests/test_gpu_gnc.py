@@ -1,4 +1,4 @@
-"""gnc_correspondences on the MI355X (dicp_amd/match.py; csrc/gnc.hip), against the g++ build of csrc/dicp_gnc.h (tests/gnc_cases.py).
+"""gnc_correspondences on the MI355X (dicp_amd/register.py; csrc/gnc.hip), against the g++ build of csrc/dicp_gnc.h (tests/gnc_cases.py).
 
 1  the kernel against the g++ build, bit for bit -- weights, rounds, status, mu, T_last and the whole trace -- for P in {0, 1, 2, 3, 4}
    and one below / at / one above the wave (64) and the slot count (1024) of the sums' tree, and 2049; n = P and n = P + 70 with dead rows

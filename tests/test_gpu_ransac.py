@@ -1,4 +1,4 @@
-"""ransac_correspondences / correspondence_residuals on the MI355X (dicp_amd/match.py; csrc/ransac.hip), against the numpy restatement
+"""ransac_correspondences / correspondence_residuals on the MI355X (dicp_amd/register.py; csrc/ransac.hip), against the numpy restatement
 tests/ransac_ref.py.
 
 1  every stage on ragged batches of three clouds, float32 and float64, pad rows holding NaN and 1e30: the packed pairs, P, the samples

@@ -1,4 +1,4 @@
-"""CPU checks of ransac_correspondences / correspondence_residuals (dicp_amd/match.py) that need no GPU.
+"""CPU checks of ransac_correspondences / correspondence_residuals (dicp_amd/register.py) that need no GPU.
 
 The rules of ``dicp_amd/csrc/dicp_ransac.h`` -- the lines the HIP kernels run -- are compiled with g++ through
 tests/hostcheck/ransac_check.cpp, run in a serial loop and held to the numpy restatement tests/ransac_ref.py: the hash and the sampler
