@@ -1287,6 +1287,25 @@ int dicp_soft_match_backward(int dtype, const void* x, const int32_t* x_rows, in
                              const void* values, int C, double tau, int form, const void* out, const void* lse, const void* grad_out, void* grad_x,
                              void* grad_y, void* grad_values, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Registration quality of H candidate poses per cloud against ONE cell grid of the target (dicp_amd/evaluate.py: evaluate_registration,
+ * information_matrix; csrc/evaluate.hip, the rules: csrc/dicp_evaluate.h).  source (N,n,c) T with c >= 3 (columns 0:3 are read),
+ * source_rows: optional (N) row counts; poses (N,H,4,4) T row-major, rows 0:3 are read, 1 <= H <= 65536; y_plans / y_keys / y_perm /
+ * y_rows4: the grid dicp_ball_grid_build made of the target (N,m,.) at the search radius.  N H ceil(n / 256) must stay below 2^31
+ * (DICP_ERR_SHAPE).
+ *   Row i < source_rows[b] is a query under pose (b, h) when q = C x + r, one fma chain per coordinate in T, is finite; its match is slot
+ *   0 of dicp_ball_query(q, k = 1), bit for bit: the first target row in (d2, index) order with d2 <= r2.  Written: counts (N,H) int32,
+ *   the matched queries; fitness (N,H) double = count / source_rows[b] (0 without rows); rmse (N,H) double = sqrt(SSE / count) (0 for
+ *   count 0); sums (N,H,10) double over the matched rows: d2, then t = the matched target point (3), then t_x t_x, t_y t_y, t_z t_z,
+ *   t_x t_y, t_x t_z, t_y t_z, all on exactly converted values; and, where not NULL, idx (N,H,n) int64 (-1 without a match) and d2
+ *   (N,H,n) T (+inf without a match).  Every sum is taken in a fixed order that depends on n alone -- per tile of 256 rows the pairwise
+ *   tree v_l + v_(l + off), off = 1 .. 128, then the tiles in ascending order from +0 --: no atomics, bit-reproducible.  Nothing is read
+ *   back.
+ *   workspace: dicp_evaluate_workspace_bytes(N, H, n) bytes (0 for bad arguments), 256-byte aligned. */
+size_t dicp_evaluate_workspace_bytes(int N, int H, int n);
+int dicp_evaluate_poses(int dtype, const void* source, int c, const int32_t* source_rows, int n, const void* poses, int H, const void* y_plans,
+                        const uint64_t* y_keys, const int32_t* y_perm, const void* y_rows4, int m, int N, void* workspace, size_t workspace_bytes,
+                        double* sums, int32_t* counts, double* fitness, double* rmse, int64_t* idx, void* d2, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
