@@ -10,16 +10,23 @@ csrc/dicp_iss.h).  Descriptors are matched and pruned on a few hundred well-spre
     idx, _ = match_features(fx[ix], fy[iy], mutual=True)                       # (or select_rows of the descriptors with the same mask)
     T0, inliers = ransac_correspondences(kx, ky, idx, 0.1)                     # -> ICP(...).icp(x, y, T_init=T0)
 
-Limits.  A neighbourhood is at most the k <= 32 NEAREST rows of the ball plus the row itself, where Open3D uses every row of the ball:
-choose the radius for the voxel size so that a ball holds about that many.  No gradients: the outputs are decisions (the kept rows of
-compute_iss_keypoints get theirs through select_rows).  No search fused into the passes: idx comes from ball_query or knn_points.
+Limits.  In the k-slot form (iss_saliency / iss_keypoints / compute_iss_keypoints by default) a neighbourhood is at most the k <= 32
+NEAREST rows of the ball plus the row itself, where Open3D uses every row of the ball: choose the radius for the voxel size so that a ball
+holds about that many, and idx comes from ball_query or knn_points (no search fused into those passes).  The whole-ball form
+(iss_saliency_ball / iss_keypoints_ball / compute_iss_keypoints(whole_ball=True); libdicp_hip.so: dicp_iss_ball_saliency /
+dicp_iss_ball_maxima, the member list: csrc/dicp_iss_ball.h) has no such limit: it walks every row of the ball on the cloud's cell grid
+and takes no index.  Its sums run over the members in cell order, so its eigenvalues differ from the k-slot form's in the last bits
+even where both see the same members.  No gradients in either form: the outputs are decisions (the kept rows of compute_iss_keypoints get
+theirs through select_rows).
 """
+import math
 import numbers
 
 import torch
 
 from . import _clouds, _lib
 from ._clouds import ROW
+from ._grid import CellGrid
 from ._ops import _DT, _p, _workspace
 from .ball import ball_query
 from .filter import select_rows
@@ -161,20 +168,131 @@ def iss_keypoints(points, idx, rows=None, salient_radius=None, non_max_radius=No
     return outs if return_saliency else outs[0]
 
 
+# ------------------------------------------------------------------ the whole-ball form
+def _check_ball_radius(radius, what, name):
+    """a finite Python float > 0 whose square is finite -> the float"""
+    r = None if radius is None else _check_radius(radius, what)
+    if r is None or not math.isfinite(r * r):
+        raise ValueError("%s: %s must be a finite float > 0 with a finite square, got %r" % (what, name, radius))
+    return r
+
+
+def _grid_radius(r, dtype):
+    """The smallest number of dtype that is not below the Python float r, the largest finite one where that would be infinite
+    (csrc/dicp_iss_ball.h: iss_ball_grid_radius): a float32 conversion can round DOWN, and the grid's cells must not be cut for less
+    than the radius asked for.  Host arithmetic on a 0-d CPU tensor: no device work."""
+    if dtype == torch.float64:
+        return r
+    big = torch.finfo(torch.float32).max
+    if r >= big:
+        return big
+    t = torch.tensor(r, dtype=torch.float32)
+    if float(t) < r:
+        t = torch.nextafter(t, torch.tensor(math.inf, dtype=torch.float32))
+    return float(t)
+
+
+def _ball_grid(x, rows_d, radius):
+    """the CellGrid of the placed batch x at the radius of a call, rounded up to x's dtype (filled on the device: no copy)"""
+    return CellGrid(x, rows_d, torch.full((1,), _grid_radius(radius, x.dtype), dtype=x.dtype, device=x.device))
+
+
+def _saliency_ball(grid, x, radius, g21, g32, min_nb, want_eig, want_cnt):
+    """-> (ws, ws_bytes, saliency (N,m), eigenvalues (N,m,3) or None, counts (N,m) int32 or None): one launch on x's grid"""
+    N, m, _ = x.shape
+    dev = x.device
+    ws_bytes = _lib.load().dicp_iss_workspace_bytes(N, m)
+    if ws_bytes == 0:
+        raise ValueError("iss_saliency_ball: N * m must stay below 2^31, got N = %d, m = %d" % (N, m))
+    ws = _workspace(ws_bytes, dev)
+    sal = torch.empty((N, m), dtype=x.dtype, device=dev)
+    eig = torch.empty((N, m, 3), dtype=x.dtype, device=dev) if want_eig else None
+    cnt = torch.empty((N, m), dtype=torch.int32, device=dev) if want_cnt else None
+    _lib.call("dicp_iss_ball_saliency", dev, _DT[x.dtype], _p(grid.plans), _p(grid.keys), _p(grid.perm), _p(grid.rows4), N, m, radius, g21, g32,
+              min_nb, _p(ws), ws_bytes, _p(sal), _p(eig), _p(cnt), None)
+    return ws, ws_bytes, sal, eig, cnt
+
+
+def iss_saliency_ball(points, radius, rows=None, gamma21=0.975, gamma32=0.975, min_neighbors=5, return_eigenvalues=False, return_counts=False):
+    """The ISS saliency of every point over EVERY row of its ball, Open3D's neighbourhood: iss_saliency without an index and without its
+    limit of 32 slots.
+
+    points, rows, gamma21, gamma32, min_neighbors, the flags and the returns: as iss_saliency.  radius: required, a finite Python float
+    > 0 whose square is finite.  Anything else is a ValueError before any device work.
+
+    Definition (csrc/dicp_iss_ball.h; tests/iss_ball_ref.py is its numpy restatement).  Everything of iss_saliency stands; only the member
+    list changes: the members of an OK row i are the row itself, then ALL other OK rows j < rows[b] of the cloud with
+    (dx dx + dy dy) + dz dz <= radius radius in double on the exactly converted inputs (inclusive; duplicates at distance 0 included), in
+    ascending (cell key, row index) order of the cloud's cell grid -- the grid ball_query builds (csrc/dicp_ball.h), at the radius
+    rounded UP to the points' dtype: cell = floor((a - o) / s) per axis in the points' dtype with o the per-axis minimum of the OK rows and
+    s = ball_R(that radius), keys compared as (cx, cy, cz).  A row is a member once; count includes the row itself.  The sums of the mean
+    and of the covariance run over the members in that order (two walks: the mean first, never raw second moments).
+
+    One grid build and one launch on the current stream; no index or distance tensor exists at any point.  A lane walks the cells that
+    can hold a member (csrc/dicp_iss_ball.h proves that none is missed) and tests every row in them, so the cost follows the rows
+    VISITED -- several times the members.  No gradients, nothing read back (a call on device tensors with device or no rows can sit in a
+    captured graph), no float atomics: bit-reproducible.
+    """
+    what = "iss_saliency_ball"
+    _check_flag(return_eigenvalues, what, "return_eigenvalues")
+    _check_flag(return_counts, what, "return_counts")
+    r = _check_ball_radius(radius, what, "radius")
+    g21, g32 = _check_gamma(gamma21, what, "gamma21"), _check_gamma(gamma32, what, "gamma32")
+    min_nb = _check_min_neighbors(min_neighbors, what)
+    form, batch, rows, lens = _clouds.check(points, rows, what)
+    on_cpu, x, rows_d = _clouds.place(batch, rows)
+    xd = x.detach()
+    _, _, sal, eig, cnt = _saliency_ball(_ball_grid(xd, rows_d, r), xd, r, g21, g32, min_nb, return_eigenvalues, return_counts)
+    outs = _clouds.restore(form, on_cpu, batch.shape[1], lens, [(ROW, t) for t in (sal, eig, cnt) if t is not None])
+    return outs if len(outs) > 1 else outs[0]
+
+
+def iss_keypoints_ball(points, salient_radius, non_max_radius=None, rows=None, gamma21=0.975, gamma32=0.975, min_neighbors=5,
+                       return_saliency=False):
+    """The ISS keypoints of every cloud as a torch.bool mask over EVERY row of the two balls: iss_saliency_ball, then iss_keypoints' rule
+    of suppression over all members within non_max_radius (None: the salient radius), on the double saliencies.
+
+    ONE grid per call, built at the larger of the two radii; each pass enumerates the cells for its own radius.  The member ORDER of the
+    saliency pass is that grid's: where non_max_radius is the larger, the saliencies can differ in their last bits from those of
+    iss_saliency_ball(points, salient_radius), whose grid is built at the salient radius.  The suppression's walk
+    stops at the first member that beats the row (the mask is then False whatever the count).  Returns as iss_keypoints; three steps on
+    the current stream (grid, saliency, maxima), nothing read back; no gradients."""
+    what = "iss_keypoints_ball"
+    _check_flag(return_saliency, what, "return_saliency")
+    r1 = _check_ball_radius(salient_radius, what, "salient_radius")
+    r2 = r1 if non_max_radius is None else _check_ball_radius(non_max_radius, what, "non_max_radius")
+    g21, g32 = _check_gamma(gamma21, what, "gamma21"), _check_gamma(gamma32, what, "gamma32")
+    min_nb = _check_min_neighbors(min_neighbors, what)
+    form, batch, rows, lens = _clouds.check(points, rows, what)
+    on_cpu, x, rows_d = _clouds.place(batch, rows)
+    xd = x.detach()
+    N, m, _ = xd.shape
+    grid = _ball_grid(xd, rows_d, max(r1, r2))
+    ws, ws_bytes, sal, _, _ = _saliency_ball(grid, xd, r1, g21, g32, min_nb, False, False)
+    mask = torch.empty((N, m), dtype=torch.bool, device=xd.device)
+    _lib.call("dicp_iss_ball_maxima", xd.device, _DT[xd.dtype], _p(grid.plans), _p(grid.keys), _p(grid.perm), _p(grid.rows4), N, m, r2, min_nb,
+              _p(ws), ws_bytes, _p(mask), None)
+    outs = _clouds.restore(form, on_cpu, batch.shape[1], lens, [(ROW, mask)] + ([(ROW, sal)] if return_saliency else []))
+    return outs if return_saliency else outs[0]
+
+
 def compute_iss_keypoints(points, salient_radius, non_max_radius=None, k=32, rows=None, gamma21=0.975, gamma32=0.975, min_neighbors=5,
-                          return_index=False):
+                          return_index=False, whole_ball=False):
     """The ISS keypoints of every cloud as points: one ball_query(points, points, max(salient_radius, non_max_radius), k) under no_grad,
     iss_keypoints on its idx with each pass cut by its own radius (ball_query keeps the NEAREST k, so the smaller ball's members are still
-    its nearest), then select_rows(points, mask).
+    its nearest), then select_rows(points, mask).  With whole_ball=True: iss_keypoints_ball (every row of the two balls, no index; k is
+    checked but not used), then select_rows.
 
     points, rows, gamma21, gamma32, min_neighbors: as iss_saliency.  salient_radius: a finite Python float > 0; non_max_radius: the same,
     or None for the salient radius.  k: an int in [1, 32]; a point finds itself first, so k - 1 slots are left for its neighbours.
+    whole_ball: True or False (anything else is a ValueError).
 
     Returns (keypoints, rows_out[, index]) as select_rows returns them: for a batch keypoints (N, m, c) zero-padded with all c columns,
     rows_out (N,) int32 and index (N, m) int64, the input row of every keypoint in order (-1 past rows_out).  The kept rows get their
     gradient through select_rows; the decision carries none.  The limits are iss_saliency's."""
     what = "compute_iss_keypoints"
     _check_flag(return_index, what, "return_index")
+    _check_flag(whole_ball, what, "whole_ball")
     if salient_radius is None:
         raise ValueError("%s: salient_radius must be a finite float > 0, got None" % what)
     r1 = _check_radius(salient_radius, what)
@@ -184,6 +302,12 @@ def compute_iss_keypoints(points, salient_radius, non_max_radius=None, k=32, row
     _check_min_neighbors(min_neighbors, what)
     _clouds._check_k(k, what, K_MIN, K_MAX)
     _clouds.check(points, rows, what)
+    if whole_ball:
+        _check_ball_radius(salient_radius, what, "salient_radius")
+        _check_ball_radius(r2, what, "non_max_radius")
+        with torch.no_grad():
+            mask = iss_keypoints_ball(points, r1, r2, rows=rows, gamma21=gamma21, gamma32=gamma32, min_neighbors=min_neighbors)
+        return select_rows(points, mask, rows=rows, return_index=return_index)
     with torch.no_grad():
         idx = ball_query(points, points, max(r1, r2), k=k, x_rows=rows, y_rows=rows)[1]
         mask = iss_keypoints(points, idx, rows=rows, salient_radius=r1, non_max_radius=r2, gamma21=gamma21, gamma32=gamma32,

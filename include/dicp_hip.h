@@ -1261,6 +1261,26 @@ int dicp_iss_saliency(int dtype, const void* points, int c, const void* idx, int
 int dicp_iss_maxima(int dtype, const void* points, int c, const void* idx, int idx64, const int32_t* rows, int N, int m, int k, double radius,
                     int min_neighbors, const void* workspace, size_t workspace_bytes, uint8_t* mask_out, void* stream);
 
+/* Whole-ball ISS keypoints (dicp_amd/iss.py: iss_saliency_ball / iss_keypoints_ball; csrc/iss_ball.hip, the member list and its coverage
+ * proof: csrc/dicp_iss_ball.h).  The rules are those of dicp_iss_saliency / dicp_iss_maxima; only the member list differs: row i itself,
+ * then EVERY other live row j of the cloud with r2 = (dx dx + dy dy) + dz dz <= radius radius in double, in ascending (cell key, row
+ * index) order -- the order of the cloud's cell grid.  No index is read or written: the two entry points walk the grid that
+ * dicp_ball_grid_build made of the SAME points and rows (plans, keys (N,P), perm (N,P), rows4 (N,P,4) T with P = dicp_ball_grid_slots(m)),
+ * built at any radius (the cells each pass visits are enumerated for its own radius; a grid built at the larger of the two radii, rounded
+ * up to T, visits the fewest rows).  A live row is a row j < rows[b] with finite coordinates: exactly the rows the grid holds.
+ * radius: finite, > 0, radius radius finite; gamma21, gamma32 in (0, 1], min_neighbors >= 1 (DICP_ERR_SHAPE).
+ * dicp_iss_ball_saliency: the double saliency of every row to `workspace` (the layout of dicp_iss_workspace_bytes(N, m)); the optional
+ *   outputs saliency_out (N,m) T, eigenvalues_out (N,m,3) T and count_out (N,m) may be NULL.  Rows outside the grid get 0 everywhere;
+ *   every element of every output is stored exactly once.
+ * dicp_iss_ball_maxima: mask_out (N,m) bytes from the workspace dicp_iss_ball_saliency left for the same grid; the radius may differ.
+ * visited: optional diagnostics, (N) counters the caller zeroed: the rows each cloud's walks visited are ADDED (integer atomics). */
+int dicp_iss_ball_saliency(int dtype, const void* plans, const uint64_t* keys, const int32_t* perm, const void* rows4, int N, int m, double radius,
+                           double gamma21, double gamma32, int min_neighbors, void* workspace, size_t workspace_bytes, void* saliency_out,
+                           void* eigenvalues_out, int32_t* count_out, unsigned long long* visited, void* stream);
+int dicp_iss_ball_maxima(int dtype, const void* plans, const uint64_t* keys, const int32_t* perm, const void* rows4, int N, int m, double radius,
+                         int min_neighbors, const void* workspace, size_t workspace_bytes, uint8_t* mask_out, unsigned long long* visited,
+                         void* stream);
+
 /* Soft descriptor matches (dicp_amd/match.py: soft_match_features; csrc/softmatch.hip, the rules: csrc/dicp_softmatch.h).  x (N,n,D) T,
  * y (N,m,D) T, values (N,m,C) T, 1 <= D <= 256, 1 <= C <= 8, tau finite and > 0 with (T)(-2.0 / tau) finite and non-zero (DICP_ERR_SHAPE);
  * x_rows / y_rows: optional (N) row counts as tgt_rows.  The score s_ij and the candidates of query i are dicp_knn_features', bit for bit.
