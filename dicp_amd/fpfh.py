@@ -15,8 +15,13 @@ FPFH is invariant to a rigid motion of points AND normals together, not to flipp
 different bins.  Two scans of one scene therefore need consistently oriented normals -- each towards its own sensor position
 (estimate_normals(viewpoint=), the moved scan with the moved viewpoint).
 
-Not built: gradients (the bins are piecewise constant: the outputs never require grad), k > 32, other descriptors (SHOT), and a ball query
-fused into the first pass.
+The k-slot form (fpfh_features / compute_fpfh by default) sees at most the k <= 32 slots of the index.  The whole-ball form
+(fpfh_features_ball / compute_fpfh(whole_ball=True); libdicp_hip.so: dicp_fpfh_ball_pack / _spfh / _combine, the near list:
+csrc/dicp_fpfh_ball.h) walks EVERY row of the ball on the cloud's cell grid, takes no index, and can describe chosen rows only (at=): the
+keypoints of compute_iss_keypoints(return_index=True, whole_ball=True).
+
+Not built: gradients (the bins are piecewise constant: the outputs never require grad), other descriptors (SHOT), a ball query fused into
+the first pass of the k-slot form, at= for the k-slot form.
 """
 import math
 
@@ -112,19 +117,135 @@ def fpfh_features(points, normals, idx, rows=None, radius=None, return_spfh=Fals
     return outs if return_spfh else outs[0]
 
 
-def compute_fpfh(points, normals, radius, k=32, rows=None):
+# ------------------------------------------------------------------ the whole-ball form
+def _check_at(at, what, form, batch):
+    """The rows to describe, in the form of the points: (q,), (N, q) or a list of (q_b,), int32 or int64, on the points' device
+    -> (batch (N, q), the q_b of a list or None); a list is padded with -1, a dead entry.  ValueError for anything invalid."""
+    is_list = isinstance(at, (list, tuple))
+    items = list(at) if is_list else [at]
+    if is_list and not items:
+        raise ValueError("%s: at is an empty list" % what)
+    for i, c in enumerate(items):
+        nm = "at[%d]" % i if is_list else "at"
+        if not isinstance(c, torch.Tensor):
+            raise ValueError("%s: %s must be a tensor, got %s" % (what, nm, type(c).__name__))
+        if c.dtype not in (torch.int32, torch.int64):
+            raise ValueError("%s: %s must be int32 or int64, got %s" % (what, nm, c.dtype))
+        if c.device != batch.device:
+            raise ValueError("%s: %s and the points must be on one device, got %s and %s" % (what, nm, c.device, batch.device))
+        if is_list and c.dim() != 1:
+            raise ValueError("%s: %s must be (q_b,), got shape %s" % (what, nm, tuple(c.shape)))
+    if not is_list and at.dim() not in (1, 2):
+        raise ValueError("%s: at must be (q,), (N, q) or a list of (q_b,), got shape %s" % (what, tuple(at.shape)))
+    mine = "list" if is_list else ("single" if at.dim() == 1 else "batch")
+    if mine != form:
+        raise ValueError("%s: at must have the form of the points (single clouds, padded batches or lists), got %s and %s" % (what, mine, form))
+    if len({c.dtype for c in items}) != 1:
+        raise ValueError("%s: the clouds of at need one dtype" % what)
+    if is_list:
+        ab, lens = torch.nn.utils.rnn.pad_sequence(items, batch_first=True, padding_value=-1), [c.shape[0] for c in items]
+    else:
+        ab, lens = (at.unsqueeze(0) if at.dim() == 1 else at), None
+    if ab.shape[0] != batch.shape[0]:
+        raise ValueError("%s: at and the points must hold the same number of clouds, got %d and %d" % (what, ab.shape[0], batch.shape[0]))
+    if ab.shape[1] < 1 or ab.shape[0] * ab.shape[1] >= 2 ** 31:
+        raise ValueError("%s: at needs at least one entry and N * q below 2^31, got shape %s" % (what, tuple(ab.shape)))
+    return ab, lens
+
+
+def _fpfh_ball(x, nrm, rows_d, radius, at, want_spfh, what):
+    """placed arguments -> (out (N,m,33) or (N,q,33) in x's dtype, spfh (N,m,33) int32 or None): the grid build and three launches on the
+    current stream"""
+    from .iss import _ball_grid
+    N, m, _ = x.shape
+    dev, dt = x.device, _DT[x.dtype]
+    ws_bytes = _lib.load().dicp_fpfh_ball_workspace_bytes(dt, N, m)
+    if ws_bytes == 0:
+        raise ValueError("%s: N * m must stay below 2^31, got N = %d, m = %d" % (what, N, m))
+    grid = _ball_grid(x, rows_d, radius)
+    ws = _workspace(ws_bytes, dev)
+    q = 0 if at is None else at.shape[1]
+    out = torch.empty((N, m if at is None else q, CHANNELS), dtype=x.dtype, device=dev)
+    spfh = torch.empty((N, m, CHANNELS), dtype=torch.int32, device=dev) if want_spfh else None
+    g = (_p(grid.plans), _p(grid.keys), _p(grid.perm), _p(grid.rows4))
+    _lib.call("dicp_fpfh_ball_pack", dev, dt, g[0], g[2], g[3], _p(nrm), N, m, _p(ws), ws_bytes)
+    _lib.call("dicp_fpfh_ball_spfh", dev, dt, *g, N, m, radius, _p(ws), ws_bytes, _p(spfh), None)
+    _lib.call("dicp_fpfh_ball_combine", dev, dt, *g, _p(at), 1 if at is not None and at.dtype == torch.int64 else 0, q, N, m, radius, _p(ws), ws_bytes,
+              _p(out), None)
+    return out, spfh
+
+
+def fpfh_features_ball(points, normals, radius, rows=None, at=None, return_spfh=False):
+    """The 33-channel FPFH descriptor over EVERY row of each point's ball, Open3D's neighbourhood: fpfh_features without an index and
+    without its limit of 32 slots -- for every row, or only for the rows `at` names.
+
+    points, normals, rows: as fpfh_features.  radius: required, a finite Python float > 0 whose square is finite.
+    at: None for a descriptor of every row, or the rows to describe as indices into the SAME cloud: (q,), (N, q) or a list of (q_b,) in
+        the form of the points, int64 or int32, on the points' device -- the `index` of select_rows / compute_iss_keypoints(return_index=
+        True) goes in unchanged.  An entry is live when 0 <= at[e] < rows[b]; every other entry gets 33 zeros, and nothing is read out of
+        range whatever at holds.  Duplicates are allowed.
+    Anything else is a ValueError before any device work.
+
+    Definition (csrc/dicp_fpfh_ball.h; tests/fpfh_ball_ref.py is its numpy restatement).  Everything of fpfh_features stands; only the
+    neighbour list changes: the near list of an OK row i is ALL other OK rows j < rows[b] of the cloud with 0 < (dx dx + dy dy) + dz dz <=
+    radius radius in double on the exactly converted inputs (exact duplicates are not near), in ascending (cell key, row index) order of
+    the cloud's cell grid -- the grid ball_query builds (csrc/dicp_ball.h), at the radius rounded UP to the points' dtype, as
+    iss_saliency_ball.  The weighted sum runs over the near list in that order.  The bin counts are 32-bit.
+
+    Returns out (m, 33) / (N, m, 33) / a list of (m_b, 33) in the points' dtype -- with at: (q, 33) / (N, q, 33) / a list of (q_b, 33),
+    entry e the descriptor of row at[e]; with return_spfh=True (out, spfh), spfh the bin counts of the first pass as contiguous int32
+    (m, 33) / (N, m, 33) / a list, for EVERY row whatever at is.
+
+    One grid build and three launches on the current stream; no index or distance tensor exists at any point.  The first pass always
+    covers every row (a row's descriptor needs the counts of all rows of its ball); the second walks only the rows asked for.  No
+    gradients: the outputs never require grad.  Nothing is read back (a call on device tensors with device or no rows can sit in a
+    captured graph); no float atomics: bit-reproducible.
+    """
+    from .iss import _check_ball_radius
+    what = "fpfh_features_ball"
+    if not isinstance(return_spfh, bool):
+        raise ValueError("%s: return_spfh must be True or False, got %r" % (what, return_spfh))
+    r = _check_ball_radius(radius, what, "radius")
+    form, batch, rows, lens = _clouds.check(points, rows, what)
+    nb = _clouds.check_table(normals, what, "normals", (form, batch, lens), 3)
+    ab, qlens = (None, None) if at is None else _check_at(at, what, form, batch)
+    on_cpu, x, rows_d = _clouds.place(batch, rows)
+    at_d = None if ab is None else ab.to(x.device).contiguous()
+    out, spfh = _fpfh_ball(x.detach(), nb.detach().to(x.device).contiguous(), rows_d, r, at_d, return_spfh, what)
+    if ab is None:
+        outs = _clouds.restore(form, on_cpu, batch.shape[1], lens, [(ROW, out)] + ([(ROW, spfh)] if return_spfh else []))
+        return outs if return_spfh else outs[0]
+    if on_cpu:
+        out = out.cpu()
+    out = [out[b, :n] for b, n in enumerate(qlens)] if form == "list" else (out[0] if form == "single" else out)
+    return (out, _clouds.restore(form, on_cpu, batch.shape[1], lens, [(ROW, spfh)])[0]) if return_spfh else out
+
+
+def compute_fpfh(points, normals, radius, k=32, rows=None, whole_ball=False, at=None):
     """fpfh_features over the neighbours within `radius`: idx = ball_query(points, points, radius, k, x_rows=rows, y_rows=rows), the
-    nearest k of them, then fpfh_features(points, normals, idx, rows=rows, radius=radius).
+    nearest k of them, then fpfh_features(points, normals, idx, rows=rows, radius=radius).  With whole_ball=True:
+    fpfh_features_ball(points, normals, radius, rows=rows, at=at) -- every row of the ball, no index; k is checked but not used.
 
     points, normals, rows: as fpfh_features.  radius: a finite Python float > 0.  k: an int in [1, 32]; a point finds itself first, so
-    k - 1 slots are left for its neighbours.  Returns the descriptors in the form of the points."""
+    k - 1 slots are left for its neighbours.  whole_ball: True or False.  at: with whole_ball=True only (a ValueError otherwise), the
+    rows to describe, as fpfh_features_ball takes them.  Returns the descriptors in the form of the points (of at, where given)."""
     what = "compute_fpfh"
+    if not isinstance(whole_ball, bool):
+        raise ValueError("%s: whole_ball must be True or False, got %r" % (what, whole_ball))
     if radius is None:
         raise ValueError("%s: radius must be a finite float > 0, got None" % what)
     radius = _check_radius(radius, what)
     _clouds._check_k(k, what, K_MIN, K_MAX)
     form, batch, _, lens = _clouds.check(points, rows, what)
     _clouds.check_table(normals, what, "normals", (form, batch, lens), 3)
+    if at is not None and not whole_ball:
+        raise ValueError("%s: at needs whole_ball=True (the k-slot form describes every row)" % what)
+    if whole_ball:
+        from .iss import _check_ball_radius
+        _check_ball_radius(radius, what, "radius")
+        if at is not None:
+            _check_at(at, what, form, batch)
+        return fpfh_features_ball(points, normals, radius, rows=rows, at=at)
     with torch.no_grad():
         idx = ball_query(points, points, radius, k=k, x_rows=rows, y_rows=rows)[1]
     return fpfh_features(points, normals, idx, rows=rows, radius=radius)

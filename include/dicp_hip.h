@@ -1281,6 +1281,33 @@ int dicp_iss_ball_maxima(int dtype, const void* plans, const uint64_t* keys, con
                          int min_neighbors, const void* workspace, size_t workspace_bytes, uint8_t* mask_out, unsigned long long* visited,
                          void* stream);
 
+/* Whole-ball FPFH descriptors, at every row or at chosen rows (dicp_amd/fpfh.py: fpfh_features_ball / compute_fpfh(whole_ball=True);
+ * csrc/fpfh_ball.hip, the near list: csrc/dicp_fpfh_ball.h).  The rules are those of dicp_fpfh_spfh / dicp_fpfh_combine; only the
+ * neighbour list differs: the NEAR LIST of an OK row i is EVERY other live row j of the cloud that is OK and has 0 < r2 = (dx dx + dy dy)
+ * + dz dz <= radius radius in double (exact duplicates are not near), in ascending (cell key, row index) order of the cloud's cell grid.
+ * No index is read or written: the entry points walk the grid that dicp_ball_grid_build made of the SAME points and rows (plans, keys
+ * (N,P), perm (N,P), rows4 (N,P,4) T with P = dicp_ball_grid_slots(m)); a grid built at the radius rounded up to T visits the fewest
+ * rows.  A live row is a row j < rows[b] with finite coordinates: exactly the rows the grid holds.  N m < 2^31; radius: finite, > 0,
+ * radius radius finite (DICP_ERR_SHAPE).  The bin counts are 32-bit: no cap on the size of a ball.
+ *   workspace: dicp_fpfh_ball_workspace_bytes(dtype, N, m) bytes (0 for bad arguments), 256-byte aligned, internal to the three calls.
+ * dicp_fpfh_ball_pack: normals (N,m,3) T and their OK flags into the workspace in the order of the grid, and the map row -> sorted slot.
+ * dicp_fpfh_ball_spfh: after the pack, the bin counts of the pairs of every row into the workspace (per sorted slot the 33 values
+ *   s[ch] = (100 cnt[ch]) / c and the OK flag) and, if spfh is not NULL, into spfh (N,m,33) int32, every element stored once (zeros for
+ *   rows outside the grid or not OK).
+ * dicp_fpfh_ball_combine: after the two, out from the workspace for the same grid and radius.  at == NULL (q must be 0): out (N,m,33) T,
+ *   one descriptor per row.  Otherwise at (N,q) int64 (at64 = 1) or int32 (at64 = 0; anything else: DICP_ERR_ENUM), q >= 1, N q < 2^31:
+ *   out (N,q,33) T, entry e the descriptor of row at[b,e] of cloud b; an entry outside 0 <= at < rows[b] (one unsigned compare, so
+ *   nothing is read out of range whatever at holds), and a row that is not OK, get 33 zeros.  Duplicates are allowed.
+ * visited: optional diagnostics, (N) counters the caller zeroed: the rows each cloud's walks visited are ADDED (integer atomics). */
+size_t dicp_fpfh_ball_workspace_bytes(int dtype, int N, int m);
+int dicp_fpfh_ball_pack(int dtype, const void* plans, const int32_t* perm, const void* rows4, const void* normals, int N, int m, void* workspace,
+                        size_t workspace_bytes, void* stream);
+int dicp_fpfh_ball_spfh(int dtype, const void* plans, const uint64_t* keys, const int32_t* perm, const void* rows4, int N, int m, double radius,
+                        void* workspace, size_t workspace_bytes, int32_t* spfh, unsigned long long* visited, void* stream);
+int dicp_fpfh_ball_combine(int dtype, const void* plans, const uint64_t* keys, const int32_t* perm, const void* rows4, const void* at, int at64, int q,
+                           int N, int m, double radius, const void* workspace, size_t workspace_bytes, void* out, unsigned long long* visited,
+                           void* stream);
+
 /* Soft descriptor matches (dicp_amd/match.py: soft_match_features; csrc/softmatch.hip, the rules: csrc/dicp_softmatch.h).  x (N,n,D) T,
  * y (N,m,D) T, values (N,m,C) T, 1 <= D <= 256, 1 <= C <= 8, tau finite and > 0 with (T)(-2.0 / tau) finite and non-zero (DICP_ERR_SHAPE);
  * x_rows / y_rows: optional (N) row counts as tgt_rows.  The score s_ij and the candidates of query i are dicp_knn_features', bit for bit.
