@@ -11,8 +11,8 @@ import threading
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 LIB_PATH = os.environ.get("DICP_HIP_LIB") or os.path.join(_HERE, "libdicp_hip.so")   # env override: A/B builds
-SOURCES = [os.path.join(_HERE, "csrc", f) for f in ("dicp_kernels.hip", "knn_f16.hip", "dicp_call.hip", "normals.hip", "voxel.hip", "knn_points.hip", "fps.hip", "ball_query.hip", "knn_grid.hip", "group.hip", "inverse.hip", "knn_det.hip", "normals_det.hip", "filter.hip", "match.hip", "ransac.hip", "compat.hip", "compat2.hip", "fpfh.hip", "softmatch.hip", "iss.hip", "gnc.hip", "evaluate.hip", "iss_ball.hip", "fpfh_ball.hip")]
-HEADERS = ([os.path.join(_HERE, "csrc", f) for f in ("dicp_math.h", "dicp_common.h", "dicp_internal.h", "dicp_fill.h", "dicp_normals.h", "dicp_voxel.h", "dicp_topk.h", "dicp_fps.h", "dicp_ball.h", "dicp_gridknn.h", "kernels_grid.h", "kernels_grid_plan.h", "dicp_group.h", "dicp_group_launch.h", "dicp_inverse.h", "dicp_knn_det.h", "kernels_normals.h", "dicp_normals_det.h", "dicp_filter.h", "dicp_match.h", "dicp_ransac.h", "dicp_compat.h", "dicp_compat2.h", "dicp_fpfh.h", "dicp_softmatch.h", "dicp_iss.h", "dicp_gnc.h", "dicp_evaluate.h", "dicp_iss_ball.h", "dicp_fpfh_ball.h")]
+SOURCES = [os.path.join(_HERE, "csrc", f) for f in ("dicp_kernels.hip", "knn_f16.hip", "dicp_call.hip", "normals.hip", "voxel.hip", "knn_points.hip", "fps.hip", "ball_query.hip", "knn_grid.hip", "group.hip", "inverse.hip", "knn_det.hip", "normals_det.hip", "filter.hip", "match.hip", "ransac.hip", "compat.hip", "compat2.hip", "fpfh.hip", "softmatch.hip", "iss.hip", "gnc.hip", "evaluate.hip", "iss_ball.hip", "fpfh_ball.hip", "normals_ball.hip")]
+HEADERS = ([os.path.join(_HERE, "csrc", f) for f in ("dicp_math.h", "dicp_common.h", "dicp_internal.h", "dicp_fill.h", "dicp_normals.h", "dicp_voxel.h", "dicp_topk.h", "dicp_fps.h", "dicp_ball.h", "dicp_gridknn.h", "kernels_grid.h", "kernels_grid_plan.h", "dicp_group.h", "dicp_group_launch.h", "dicp_inverse.h", "dicp_knn_det.h", "kernels_normals.h", "dicp_normals_det.h", "dicp_filter.h", "dicp_match.h", "dicp_ransac.h", "dicp_compat.h", "dicp_compat2.h", "dicp_fpfh.h", "dicp_softmatch.h", "dicp_iss.h", "dicp_gnc.h", "dicp_evaluate.h", "dicp_iss_ball.h", "dicp_fpfh_ball.h", "dicp_normals_ball.h")]
            + [os.path.join(_HERE, "csrc", "kernels_%s.h" % f) for f in ("setup", "search", "setup_sort", "rows", "accumulate", "backward", "soft_svd", "host")]
            + [os.path.join(_ROOT, "include", "dicp_hip.h")])
 
@@ -320,6 +320,10 @@ _SIGNATURES = {
     "dicp_fpfh_ball_pack": ([i32, vp, vp, vp, vp, i32, i32, vp, ctypes.c_size_t, vp], ctypes.c_int),
     "dicp_fpfh_ball_spfh": ([i32, vp, vp, vp, vp, i32, i32, f64, vp, ctypes.c_size_t, vp, vp, vp], ctypes.c_int),
     "dicp_fpfh_ball_combine": ([i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, f64, vp, ctypes.c_size_t, vp, vp, vp], ctypes.c_int),
+    "dicp_normals_ball_workspace_bytes": ([i32, i32], ctypes.c_size_t),
+    "dicp_normals_ball_forward": ([i32, vp, vp, vp, vp, i32, i32, f64, i32, vp, i32, vp, ctypes.c_size_t, vp, vp, vp, vp, vp, vp], ctypes.c_int),
+    "dicp_normals_ball_records": ([i32, vp, vp, vp, i32, i32, vp, vp, vp, ctypes.c_size_t, vp, vp], ctypes.c_int),
+    "dicp_normals_ball_gather": ([i32, vp, vp, vp, vp, i32, i32, i32, f64, vp, vp, vp, vp], ctypes.c_int),
     "dicp_evaluate_workspace_bytes": ([i32, i32, i32], ctypes.c_size_t),
     "dicp_evaluate_poses": ([i32, vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, i32, i32, vp, ctypes.c_size_t, vp, vp, vp, vp, vp, vp, vp], ctypes.c_int),
 }

@@ -8,7 +8,13 @@ from the inverted index of the neighbours (dicp_normals_backward_records / dicp_
     from dicp_amd.normals import estimate_normals
     nrm = estimate_normals(pts, k=16)
     target = torch.cat((pts, nrm), dim=-1)        # -> ICP(icp_type='pt2pl').icp(source, target, ...)
+
+`estimate_normals_ball` takes EVERY row of a ball of radius R instead of the k <= 32 nearest rows -- the neighbourhood of
+iss_keypoints_ball and fpfh_features_ball (dicp_normals_ball_forward / _records / _gather; the rules: csrc/dicp_normals_ball.h) -- and its
+gradient is a gather over each row's own ball walk: no index, no atomics, bit-reproducible with no switch.
 """
+
+import numbers
 
 import torch
 
@@ -16,6 +22,7 @@ from . import _clouds, _lib
 from ._clouds import ROW, _check_method
 from ._ops import _DT, _p, _workspace
 from .group import _invert
+from .iss import _ball_grid, _check_ball_radius, _check_flag
 
 REC = 13                # NRM_REC (csrc/dicp_normals_det.h): the doubles of a row's record, G6[0:6], mu[6:9], p[9:12], f[12]
 
@@ -164,5 +171,111 @@ def estimate_normals(points, k=16, viewpoint=None, rows=None, return_curvature=F
     vp_d = vp.detach().to(device=x.device, dtype=x.dtype).contiguous() if vp is not None else None
     nrm, curv, nbr = _Normals.apply(x, rows_d, vp_d, k, bool(return_neighbors), method == "grid", _visited, _passes, deterministic, _records)
     outs = [(ROW, nrm)] + ([(ROW, curv)] if return_curvature else []) + ([(ROW, nbr)] if return_neighbors else [])
+    outs = _clouds.restore(form, on_cpu, m, lens, outs)
+    return outs[0] if len(outs) == 1 else outs
+
+
+# ------------------------------------------------------------------ the whole-ball form
+class _NormalsBall(torch.autograd.Function):
+    """(N,m,c) points -> (normals (N,m,3), curvature (N,m), eigenvalues (N,m,3), counts (N,m) int32): one grid build and one launch on the
+    current stream; the backward is two launches (records, gather) on the grid and the state the forward kept.  visited: optional
+    ((N,), (N,)) int64 counters of the forward's and the gather's walks; records: an optional list that backward appends its records to."""
+
+    @staticmethod
+    def forward(ctx, pts, rows, vp, radius, min_nb, visited, records):
+        N, m, c = pts.shape
+        dev = pts.device
+        dt = _DT[pts.dtype]
+        ws_bytes = _lib.load().dicp_normals_ball_workspace_bytes(N, m)
+        if ws_bytes == 0:
+            raise ValueError("estimate_normals_ball: N * m must stay below 2^31, got N = %d, m = %d" % (N, m))
+        grid = _ball_grid(pts, rows, radius)
+        ws = _workspace(ws_bytes, dev)
+        nrm = torch.empty((N, m, 3), dtype=pts.dtype, device=dev)
+        curv = torch.empty((N, m), dtype=pts.dtype, device=dev)
+        eig = torch.empty((N, m, 3), dtype=pts.dtype, device=dev)
+        cnt = torch.empty((N, m), dtype=torch.int32, device=dev)
+        _lib.call("dicp_normals_ball_forward", dev, dt, _p(grid.plans), _p(grid.keys), _p(grid.perm), _p(grid.rows4), N, m, radius, min_nb, _p(vp),
+                  int(vp is not None and vp.dim() == 2), _p(ws), ws_bytes, _p(nrm), _p(curv), _p(eig), _p(cnt),
+                  _p(visited[0]) if visited is not None else None)
+        ctx.grid, ctx.ws, ctx.ws_bytes = grid, ws, ws_bytes         # (kept off the saved-tensor version checks, as _Normals keeps ctx.ws)
+        ctx.shape, ctx.radius, ctx.visited, ctx.records = (N, m, c), radius, visited, records
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(eig, cnt)
+        return nrm, curv, eig, cnt
+
+    @staticmethod
+    def backward(ctx, g_nrm, g_curv, _g_eig, _g_cnt):
+        if g_nrm is None and g_curv is None:
+            return (None,) * 7
+        grid, ws = ctx.grid, ctx.ws
+        N, m, c = ctx.shape
+        dev = ws.device
+        dtype = g_nrm.dtype if g_nrm is not None else g_curv.dtype
+        dt = _DT[dtype]
+        g_nrm = g_nrm.contiguous() if g_nrm is not None else None
+        g_curv = g_curv.contiguous() if g_curv is not None else None
+        rec = torch.empty((N, grid.slots, REC), dtype=torch.float64, device=dev)
+        _lib.call("dicp_normals_ball_records", dev, dt, _p(grid.plans), _p(grid.perm), _p(grid.rows4), N, m, _p(g_nrm), _p(g_curv), _p(ws), ctx.ws_bytes,
+                  _p(rec))
+        grad = torch.empty((N, m, c), dtype=dtype, device=dev)
+        _lib.call("dicp_normals_ball_gather", dev, dt, _p(grid.plans), _p(grid.keys), _p(grid.perm), _p(grid.rows4), N, m, c, ctx.radius, _p(rec),
+                  _p(grad), _p(ctx.visited[1]) if ctx.visited is not None else None)
+        if ctx.records is not None:
+            ctx.records.append((rec, grid))
+        return (grad,) + (None,) * 6
+
+
+def estimate_normals_ball(points, radius, viewpoint=None, rows=None, min_neighbors=3, return_curvature=False, return_eigenvalues=False,
+                          return_counts=False, _visited=None, _records=None):
+    """Unit surface normals of every point from EVERY row of its ball of radius `radius`: Open3D's estimate_normals with a radius search,
+    over the same support as iss_keypoints_ball and fpfh_features_ball at that radius.
+
+    points, rows, viewpoint: exactly as estimate_normals.  radius: required, a finite Python float > 0 whose square is finite.
+    min_neighbors: an int >= 3; it counts the row itself.  The flags are bools.  Anything else is a ValueError before any device work.
+
+    Definition (csrc/dicp_normals_ball.h; tests/normals_ball_ref.py is its numpy restatement), in double on the exactly converted inputs.
+    The members of a row, their order, the mean and the covariance are iss_saliency_ball's, bit for bit: the row itself, then all other
+    live rows (j < rows[b], three finite coordinates) with (dx dx + dy dy) + dz dz <= radius radius, in ascending (cell key, row index)
+    order of the cloud's cell grid at the radius rounded UP to the points' dtype; two walks, never raw second moments.  The eigen-system
+    is that pass's cyclic Jacobi with the rotations also applied to a matrix of eigenvectors, so the eigenvalues equal
+    iss_saliency_ball(return_eigenvalues=True)'s bits.  n = s v_0 with s = +-1 so that n . (viewpoint - p_i) >= 0 (on exactly 0: the
+    first non-zero component positive); curvature = lam_0 / ((lam_0 + lam_1) + lam_2), 0 unless the trace is > 0.  A row that is not
+    live gets a zero normal, curvature 0, eigenvalues 0, count 0 and no gradient; a live row with fewer than min_neighbors members a zero
+    normal and curvature 0, its count and eigenvalues are still reported.
+
+    Returns normals (..., m, 3) in the points' dtype (a list for a list); with the flags, in this order, also curvature (..., m),
+    eigenvalues (..., m, 3) ascending and counts (..., m) int32.
+
+    Gradients flow to points[..., :3] (zero for the other columns); the viewpoint, the membership and the sign get none.  A row whose two
+    smallest eigenvalues are not separated (lam_1 - lam_0 <= tau trace, tau = 1e-6 for float32 and 1e-12 for float64, as estimate_normals),
+    with fewer than min_neighbors members, a zero trace or all-zero cotangents contributes nothing (it still receives the terms of the
+    members whose balls hold it: their normals depend on it).  Ball membership is symmetric -- the double r2 of (i, j) and of (j, i)
+    are the same bits -- so the gradient of row j is a GATHER over j's own ball walk: the sum over its
+    members i, in j's member order (j first), of f_i ((G_a0 d_0 + G_a1 d_1) + G_a2 d_2), d = (p_j - p_i) - mu_i, f_i = 2 / n_i, G = dL/dC of
+    row i, in double from +0, rounded once to the points' dtype.  No neighbour index, no inverted index, no float atomics, no zero fill:
+    every element is stored exactly once and the result is bit-reproducible by construction.
+
+    One grid build and one launch per call on the current stream (the backward: two launches, one of them a walk); no index or distance
+    tensor exists at any point and nothing is read back, so a call on device tensors with device rows or no rows can sit in a captured
+    graph, forward and backward.  A lane tests every row of the cells that can hold a member: the cost follows the rows visited.
+    """
+    what = "estimate_normals_ball"
+    for name, flag in (("return_curvature", return_curvature), ("return_eigenvalues", return_eigenvalues), ("return_counts", return_counts)):
+        _check_flag(flag, what, name)
+    r = _check_ball_radius(radius, what, "radius")
+    if isinstance(min_neighbors, bool) or not isinstance(min_neighbors, numbers.Integral) or min_neighbors < 3 or min_neighbors > 2 ** 31 - 1:
+        raise ValueError("%s: min_neighbors must be an int >= 3, got %r" % (what, min_neighbors))
+    form, batch, rows, lens = _clouds.check(points, rows, what, flat_rows=True)
+    N, m = batch.shape[0], batch.shape[1]
+    vp = None
+    if viewpoint is not None:
+        vp = torch.as_tensor(viewpoint)
+        if vp.dtype.is_complex or vp.dtype == torch.bool or vp.shape not in ((3,), (N, 3)):
+            raise ValueError("%s: viewpoint must be (3,) or (%d, 3), got shape %s" % (what, N, tuple(vp.shape)))
+    on_cpu, x, rows_d = _clouds.place(batch, rows)
+    vp_d = vp.detach().to(device=x.device, dtype=x.dtype).contiguous() if vp is not None else None
+    nrm, curv, eig, cnt = _NormalsBall.apply(x, rows_d, vp_d, r, int(min_neighbors), _visited, _records)
+    outs = [(ROW, nrm)] + [(ROW, t) for t, on in ((curv, return_curvature), (eig, return_eigenvalues), (cnt, return_counts)) if on]
     outs = _clouds.restore(form, on_cpu, m, lens, outs)
     return outs[0] if len(outs) == 1 else outs

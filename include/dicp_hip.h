@@ -1308,6 +1308,42 @@ int dicp_fpfh_ball_combine(int dtype, const void* plans, const uint64_t* keys, c
                            int N, int m, double radius, const void* workspace, size_t workspace_bytes, void* out, unsigned long long* visited,
                            void* stream);
 
+/* Whole-ball surface normals with a gather backward (dicp_amd/normals.py: estimate_normals_ball; csrc/normals_ball.hip, the rules:
+ * csrc/dicp_normals_ball.h).  The member list of a row is dicp_iss_ball_saliency's -- row i itself, then EVERY other live row j of the
+ * cloud with r2 = (dx dx + dy dy) + dz dz <= radius radius in double, in ascending (cell key, row index) order --, its mean and covariance
+ * are that pass's bit for bit, and the eigen-system is its cyclic Jacobi with the rotations also applied to a matrix of eigenvectors.  No
+ * index is read or written: the entry points walk the grid that dicp_ball_grid_build made of the SAME points and rows (plans, keys (N,P),
+ * perm (N,P), rows4 (N,P,4) T with P = dicp_ball_grid_slots(m)); a grid built at the radius rounded up to T visits the fewest rows.
+ * N m < 2^31; radius: finite, > 0, radius radius finite; min_neighbors >= 3 (DICP_ERR_SHAPE).
+ *   workspace: dicp_normals_ball_workspace_bytes(N, m) bytes (0 for bad arguments or N m >= 2^31), 256-byte aligned: the state of every
+ *   sorted slot (scaled covariance, mean, count, sign) that the forward leaves for dicp_normals_ball_records.
+ * dicp_normals_ball_forward: normals_out (N,m,3) T = s v_0, the eigenvector of the smallest eigenvalue signed to face viewpoint ((3) T,
+ *   or (N,3) T with viewpoint_per_cloud = 1; NULL: the origin; on a dot product of exactly 0 the first non-zero component is made
+ *   positive); the optional curvature_out (N,m) T = lam_0 / ((lam_0 + lam_1) + lam_2) (0 unless the trace is > 0), eigenvalues_out
+ *   (N,m,3) T ascending and count_out (N,m), the members with the row itself, may be NULL.  A row outside the grid gets 0 everywhere; a
+ *   live row with fewer than min_neighbors members a zero normal and curvature 0, its count and eigenvalues are reported.  Every element
+ *   of every output is stored exactly once.
+ * dicp_normals_ball_records: from the workspace the forward left for the same grid and the cotangents g_normals (N,m,3) T and
+ *   g_curvature (N,m) T (either may be NULL), records (N,P,13) doubles IN SORTED-SLOT ORDER: [0..6) G = dL/dC symmetrised, [6..9) mu,
+ *   [9..12) the row's coordinates, [12] f = 2 / count, or f = 0 with G = mu = 0 where the row contributes nothing (outside the grid,
+ *   fewer than min_neighbors members, cotangents absent or all zero, lam_1 - lam_0 <= tau trace with tau = 1e-6 (float32) / 1e-12
+ *   (float64), zero trace).  Every slot's record is stored.  No walk.
+ * dicp_normals_ball_gather: grad_out (N,m,c) T, c >= 3: row j's columns 0:3 receive the sum over the members i of j, in j's own member
+ *   order (j first), of f_i ((G_a0 d_0 + G_a1 d_1) + G_a2 d_2) with d = (p_j - p_i) - mu_i, in double from +0, rounded once to T;
+ *   members with f_i = 0 are skipped.  Ball membership is symmetric (the double r2 of (i, j) and of (j, i) are the same bits), so this
+ *   is the sum over the rows whose ball holds j: no index, no atomics, no zero fill; every element is stored exactly once, the zeros of
+ *   rows outside the grid and of columns >= 3 included.  radius: the forward's.
+ * visited: optional diagnostics, (N) counters the caller zeroed: the rows each cloud's walks visited are ADDED (integer atomics). */
+size_t dicp_normals_ball_workspace_bytes(int N, int m);
+int dicp_normals_ball_forward(int dtype, const void* plans, const uint64_t* keys, const int32_t* perm, const void* rows4, int N, int m, double radius,
+                              int min_neighbors, const void* viewpoint, int viewpoint_per_cloud, void* workspace, size_t workspace_bytes,
+                              void* normals_out, void* curvature_out, void* eigenvalues_out, int32_t* count_out, unsigned long long* visited,
+                              void* stream);
+int dicp_normals_ball_records(int dtype, const void* plans, const int32_t* perm, const void* rows4, int N, int m, const void* g_normals,
+                              const void* g_curvature, const void* workspace, size_t workspace_bytes, double* records, void* stream);
+int dicp_normals_ball_gather(int dtype, const void* plans, const uint64_t* keys, const int32_t* perm, const void* rows4, int N, int m, int c,
+                             double radius, const double* records, void* grad_out, unsigned long long* visited, void* stream);
+
 /* Soft descriptor matches (dicp_amd/match.py: soft_match_features; csrc/softmatch.hip, the rules: csrc/dicp_softmatch.h).  x (N,n,D) T,
  * y (N,m,D) T, values (N,m,C) T, 1 <= D <= 256, 1 <= C <= 8, tau finite and > 0 with (T)(-2.0 / tau) finite and non-zero (DICP_ERR_SHAPE);
  * x_rows / y_rows: optional (N) row counts as tgt_rows.  The score s_ij and the candidates of query i are dicp_knn_features', bit for bit.
